@@ -88,7 +88,12 @@ def parse():
                     help="A/B runs: d2r_gemm_tuning tile code(s) applied before the first step (e.g. 120: grouped launches off, 102: 128-wide weight gradients)")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("D2R_BENCH_GRAPH", "0")),
                     help="1: replay the step from a captured hipGraph (fwd+bwd[+AdamW at N=1]); 0 (default): eager launches — measured faster on ROCm 7.2, see DESIGN.md")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def synthetic_batch(B, L, image_size, device, seed, classes=3):
@@ -163,6 +168,37 @@ def cpu_baseline(args, sd_cpu):
                       f"of {os.cpu_count()} host CPUs ({cpu_model})"}
 
 
+DUMP_SAMPLE = 1 << 20  # elements of each flat optimiser buffer written by --dump-outputs (4 MB each in float32)
+
+
+def dump_outputs(out_dir, loss, logits, store, opt):
+    """What the timed step hands its caller, from the LAST timed step: the loss and the logits of the forward, and - the
+    step's real product - the updated fp32 master weights and AdamW moments.  The flat buffers hold ~10^8 elements, so a
+    fixed sample of DUMP_SAMPLE of them is written (numpy seed 0; positions over the live parameters ordered by name, so
+    the sample does not depend on the flat-buffer layout).  Everything is float32 and well below 64 MB."""
+    import numpy as np
+    import torch
+    if not os.path.isdir(out_dir):  # a directory made here holds only dumps: keep it out of git status, as pytest does its cache
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:
+            f.write("*\n")
+    entries = sorted((n, o, k) for n, _, o, k, _ in store.entries)
+    numel = np.array([k for _, _, k in entries], dtype=np.int64)
+    offset = np.array([o for _, o, _ in entries], dtype=np.int64)
+    start = np.cumsum(numel) - numel
+    pos = np.unique(np.random.default_rng(0).integers(0, int(numel.sum()), DUMP_SAMPLE, dtype=np.int64))
+    e = np.searchsorted(start, pos, side="right") - 1
+    idx = torch.from_numpy(offset[e] + (pos - start[e])).to(store.flat_w.device)
+    arrays = {"loss": loss.detach().float().reshape(1), "logits": logits.detach().float(),
+              "weights_sample": store.flat_w[idx], "adam_m_sample": opt.m[idx], "adam_v_sample": opt.v[idx]}
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without torch.distributed.run: start the N ranks as a CHILD process (this process has
     not touched the GPU — torch is not even imported yet — and never re-execs), relay its output and exit code."""
@@ -226,9 +262,12 @@ def main():
     dp.broadcast_parameters()
     batch = synthetic_batch(args.batch, args.seq, args.image_size, dev, seed=rank, classes=args.classes)
 
+    last = {}  # the logits of the latest eager step (--dump-outputs)
+
     def step():
         dp.begin_step()
         loss, logits = model(*batch)
+        last["logits"] = logits
         opt.backward(loss)
         dp.reduce_gradients()
         opt.step()
@@ -306,6 +345,10 @@ def main():
     ms = dt / args.steps * 1e3
     value = world * args.batch * args.steps / dt
     log(f"timed region: {args.steps} steps, {ms:.2f} ms/step, {value:.1f} samples/s (host enqueue {host_ms:.2f} ms/step)")
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before the legs below move the weights on
+        dumped = dump_outputs(args.dump_outputs, loss, static["logits"] if args.graph else last["logits"], store, opt)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
 
     # From here on no rank issues a gradient collective any more (the legs below are local measurements; rank 0 runs
     # one more pass than the others): switch the overlap hooks off on every rank.
@@ -341,6 +384,7 @@ def main():
                    "global_batch": world * args.batch, "seq_len": args.seq, "parallelism": f"dp{world}"},
         "final_loss": round(loss_val, 5), "launch": "hipGraph replay" if args.graph else "eager",
         "host_enqueue_ms_per_step": round(host_ms, 3),
+        "dump_outputs": {"dir": args.dump_outputs, "arrays": dumped} if dumped is not None else None,
         "fwd_bwd_only": {"ms_per_step_per_rank": round(fb_ms, 3), "samples_per_s": round(world * args.batch / fb_ms * 1e3, 2),
                          "note": "no optimiser step, no gradient all-reduce; measured on rank 0's clock"},
     }
