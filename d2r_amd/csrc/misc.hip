@@ -286,6 +286,13 @@ __device__ __forceinline__ void row_logsoftmax_stats(const float* x, int n, int 
   lse = logf(s);
 }
 
+// log m, m = (p + q) / 2.  When p and q are both subnormal, (p + q) / 2 can round to 0 while one of them is not 0, and
+// p (log p - log m) became inf.  That case alone takes log m from the log-probabilities, so every finite result is unchanged.
+__device__ __forceinline__ float js_log_mid(float pp, float qq, float logp, float logq) {
+  const float m = 0.5f * (pp + qq);
+  return m > 0.f ? logf(m) : fmaxf(logp, logq) + log1pf(expf(-fabsf(logp - logq))) - 0.69314718f;
+}
+
 __global__ __launch_bounds__(1024) void jsdiv_fwd_kernel(const float* __restrict__ P, const float* __restrict__ Q, int B,
                                                          float* __restrict__ out) {
   __shared__ float sh[16];
@@ -300,7 +307,7 @@ __global__ __launch_bounds__(1024) void jsdiv_fwd_kernel(const float* __restrict
     for (int k = lane; k < B; k += 64) {
       const float logp = p[k] - mp - lp, logq = q[k] - mq - lq;
       const float pp = expf(logp), qq = expf(logq);
-      const float logm = logf(0.5f * (pp + qq));
+      const float logm = js_log_mid(pp, qq, logp, logq);
       acc += (pp > 0.f ? pp * (logp - logm) : 0.f) + (qq > 0.f ? qq * (logq - logm) : 0.f);
     }
   }
@@ -324,7 +331,7 @@ __global__ __launch_bounds__(1024) void jsdiv_bwd_kernel(const float* __restrict
     for (int k = lane; k < B; k += 64) {
       const float logp = p[k] - mp - lp, logq = q[k] - mq - lq;
       const float pp = expf(logp), qq = expf(logq);
-      const float logm = logf(0.5f * (pp + qq));
+      const float logm = js_log_mid(pp, qq, logp, logq);
       dp += pp > 0.f ? pp * (logp - logm) : 0.f;
       dq += qq > 0.f ? qq * (logq - logm) : 0.f;
     }
@@ -333,7 +340,7 @@ __global__ __launch_bounds__(1024) void jsdiv_bwd_kernel(const float* __restrict
     for (int k = lane; k < B; k += 64) {
       const float logp = p[k] - mp - lp, logq = q[k] - mq - lq;
       const float pp = expf(logp), qq = expf(logq);
-      const float logm = logf(0.5f * (pp + qq));
+      const float logm = js_log_mid(pp, qq, logp, logq);
       dP[(int64_t)r * B + k] = pp > 0.f ? sc * pp * ((logp - logm) - dp) : 0.f;
       dQ[(int64_t)r * B + k] = qq > 0.f ? sc * qq * ((logq - logm) - dq) : 0.f;
     }
