@@ -81,6 +81,11 @@ class HeadDesc(C.Structure):
                 ("scratch_bytes", sz), ("d_logits", vp), ("d_pooled", vp)]
 
 
+class ClipImageDesc(C.Structure):
+    _fields_ = [("src_offset", i64)] + [(n, i32) for n in ("H", "W", "rh", "rw", "top", "left", "kx", "ky", "bx", "cx", "by", "cy",
+                                                          "row0", "nrows")] + [("ws_offset", i64)]
+
+
 # name -> (restype, argtypes); every symbol include/d2r_hip.h declares
 SIGNATURES = {
     "d2r_head_arena_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
@@ -168,6 +173,8 @@ SIGNATURES = {
     "d2r_bert_embed_fwd": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "d2r_bert_embed_bwd": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, i64, vp, vp, vp, vp]),
     "d2r_patchify": (i32, [i32, vp, i32, i32, i32, i32, vp, vp]),
+    "d2r_clip_preprocess_ws_bytes": (sz, [C.POINTER(ClipImageDesc), i32, i32]),
+    "d2r_clip_preprocess": (i32, [vp, i64, C.POINTER(ClipImageDesc), vp, i32, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
     "d2r_clip_embed_finish": (i32, [i32, vp, vp, vp, i32, i32, i32, vp]),
     "d2r_clip_embed_bwd": (i32, [i32, vp, i32, i32, i32, vp, vp, vp]),
     "d2r_adamw_step": (i32, [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, i64, f32, vp, vp]),

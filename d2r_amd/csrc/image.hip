@@ -1,0 +1,153 @@
+// image.hip — CLIP image preprocessing on the device (processor/dataset.py:87-95): Pillow's antialiased fixed-point bicubic
+// resize, center crop, rescale and normalisation of a batch of decoded uint8 RGB images of different sizes, bit-identical to
+// CLIPImageProcessor.  Integer multiply-accumulate only; the float64 coefficient tables are built on the host.
+//
+// Pillow (ImagingResample, 8 bits per channel) resizes in two separable passes: horizontal first, into a uint8 image, then
+// vertical from that image.  Each pass computes, per output pixel, 2^21 + sum_t in[xmin + t] * k[t] in int32 with 22-bit weights
+// and clips (>> 22) to uint8.  An output pixel depends only on its own weights, so computing the crop alone is exact: pass 1 runs
+// on the source rows the crop rows' vertical support touches, S crop columns wide, into the workspace; pass 2 runs the vertical
+// weights over those rows and maps every (channel, uint8) pair through the normalisation table.
+#include "common.h"
+
+namespace {
+
+constexpr int HROWS = 4;  // source rows per pass-1 workgroup: each weight is loaded once for HROWS rows
+
+__device__ __forceinline__ int clip8(int v) { return v >= (1 << 30) ? 255 : (v <= 0 ? 0 : v >> 22); }
+
+// pass 1: ws[r, j, c] = clip8(sum_t src[row0 + r, xmin_j + t, c] * kx_j[t]) for r < nrows, j < S
+__global__ __launch_bounds__(256) void clip_hpass_kernel(const uint8_t* __restrict__ src, const d2r_clip_image_desc* __restrict__ desc,
+                                                         const int32_t* __restrict__ tab, int S, uint8_t* __restrict__ ws) {
+  const d2r_clip_image_desc d = desc[blockIdx.y];
+  const int r0 = blockIdx.x * HROWS;
+  if (r0 >= d.nrows) return;
+  const int nr = min(HROWS, d.nrows - r0);
+  const int64_t pitch = (int64_t)d.W * 3;
+  const uint8_t* in = src + d.src_offset + (int64_t)(d.row0 + r0) * pitch;
+  uint8_t* o = ws + d.ws_offset + (int64_t)r0 * S * 3;
+  for (int j = threadIdx.x; j < S; j += 256) {
+    const int xmin = tab[d.bx + 2 * j], n = tab[d.bx + 2 * j + 1];
+    const int32_t* k = tab + d.cx + (int64_t)j * d.kx;
+    int acc[HROWS][3];
+#pragma unroll
+    for (int r = 0; r < HROWS; ++r) acc[r][0] = acc[r][1] = acc[r][2] = 1 << 21;
+    const uint8_t* p = in + xmin * 3;
+    for (int t = 0; t < n; ++t, p += 3) {
+      const int w = k[t];
+#pragma unroll
+      for (int r = 0; r < HROWS; ++r) {
+        const uint8_t* q = p + (r < nr ? r : nr - 1) * pitch;  // rows past the image's last are read again, not written
+        acc[r][0] += (int)q[0] * w;
+        acc[r][1] += (int)q[1] * w;
+        acc[r][2] += (int)q[2] * w;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < HROWS; ++r) {
+      if (r < nr) {
+        uint8_t* q = o + ((int64_t)r * S + j) * 3;
+        q[0] = (uint8_t)clip8(acc[r][0]);
+        q[1] = (uint8_t)clip8(acc[r][1]);
+        q[2] = (uint8_t)clip8(acc[r][2]);
+      }
+    }
+  }
+}
+
+// pass 2: out[b, c, i, j] = lut[c, clip8(sum_t ws[ymin_i - row0 + t, j, c] * ky_i[t])]
+__global__ __launch_bounds__(256) void clip_vpass_kernel(const d2r_clip_image_desc* __restrict__ desc, const int32_t* __restrict__ tab,
+                                                         const uint8_t* __restrict__ ws, const float* __restrict__ lut, int S,
+                                                         float* __restrict__ out) {
+  __shared__ float sl[3 * 256];
+  for (int i = threadIdx.x; i < 3 * 256; i += 256) sl[i] = lut[i];
+  __syncthreads();
+  const d2r_clip_image_desc d = desc[blockIdx.y];
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= S * S) return;
+  const int i = idx / S, j = idx - i * S;
+  const int ymin = tab[d.by + 2 * i] - d.row0, n = tab[d.by + 2 * i + 1];
+  const int32_t* k = tab + d.cy + (int64_t)i * d.ky;
+  const int64_t pitch = (int64_t)S * 3;
+  const uint8_t* p = ws + d.ws_offset + (int64_t)ymin * pitch + j * 3;
+  int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+  for (int t = 0; t < n; ++t, p += pitch) {
+    const int w = k[t];
+    a0 += (int)p[0] * w;
+    a1 += (int)p[1] * w;
+    a2 += (int)p[2] * w;
+  }
+  const int64_t plane = (int64_t)S * S;
+  float* o = out + (int64_t)blockIdx.y * 3 * plane + idx;
+  o[0] = sl[clip8(a0)];
+  o[plane] = sl[256 + clip8(a1)];
+  o[2 * plane] = sl[512 + clip8(a2)];
+}
+
+// every bound the kernels rely on, checked on the host copies; *max_rows = the largest nrows
+int check_descs(const d2r_clip_image_desc* h, int B, int S, int64_t src_bytes, const int32_t* ht, int64_t tab_len, size_t ws_bytes,
+                int* max_rows) {
+  int64_t ws_end = 0;
+  *max_rows = 0;
+  for (int b = 0; b < B; ++b) {
+    const d2r_clip_image_desc& d = h[b];
+    D2R_REQUIRE(d.H >= 1 && d.W >= 1 && d.src_offset >= 0 && d.src_offset + (int64_t)d.H * d.W * 3 <= src_bytes,
+                "d2r_clip_preprocess: image %d (%d x %d at byte %lld) lies outside the %lld source bytes", b, d.H, d.W,
+                (long long)d.src_offset, (long long)src_bytes);
+    D2R_REQUIRE(d.rh >= S && d.rw >= S && d.top >= 0 && d.left >= 0 && d.top + S <= d.rh && d.left + S <= d.rw,
+                "d2r_clip_preprocess: image %d: the %d x %d crop at (%d, %d) does not fit the %d x %d resized image", b, S, S, d.top,
+                d.left, d.rh, d.rw);
+    D2R_REQUIRE(d.kx >= 1 && d.ky >= 1 && d.row0 >= 0 && d.nrows >= 1 && d.row0 + d.nrows <= d.H,
+                "d2r_clip_preprocess: image %d: bad taps (%d, %d) or source rows [%d, %d)", b, d.kx, d.ky, d.row0, d.row0 + d.nrows);
+    const int64_t spans[4][2] = {{d.bx, 2LL * S}, {d.cx, (int64_t)S * d.kx}, {d.by, 2LL * S}, {d.cy, (int64_t)S * d.ky}};
+    for (const auto& s : spans)
+      D2R_REQUIRE(s[0] >= 0 && s[0] + s[1] <= tab_len, "d2r_clip_preprocess: image %d: table span [%lld, %lld) outside %lld entries", b,
+                  (long long)s[0], (long long)(s[0] + s[1]), (long long)tab_len);
+    for (int j = 0; j < S; ++j) {
+      const int lo = ht[d.bx + 2 * j], n = ht[d.bx + 2 * j + 1];
+      D2R_REQUIRE(lo >= 0 && n >= 1 && n <= d.kx && (int64_t)lo + n <= d.W,
+                  "d2r_clip_preprocess: image %d, column %d: support [%d, +%d) outside the %d columns or over %d taps", b, j, lo, n, d.W, d.kx);
+    }
+    for (int i = 0; i < S; ++i) {
+      const int lo = ht[d.by + 2 * i], n = ht[d.by + 2 * i + 1];
+      D2R_REQUIRE(lo >= d.row0 && n >= 1 && n <= d.ky && (int64_t)lo + n <= (int64_t)d.row0 + d.nrows,
+                  "d2r_clip_preprocess: image %d, row %d: support [%d, +%d) outside the rows [%d, %d) or over %d taps", b, i, lo, n,
+                  d.row0, d.row0 + d.nrows, d.ky);
+    }
+    D2R_REQUIRE(d.ws_offset >= ws_end, "d2r_clip_preprocess: image %d: workspace region overlaps the previous image's", b);
+    ws_end = d.ws_offset + (int64_t)d.nrows * S * 3;
+    if (ws_end > (int64_t)ws_bytes)
+      return d2r_fail(D2R_ERR_WORKSPACE, "d2r_clip_preprocess: workspace of %zu bytes, image %d needs %lld", ws_bytes, b, (long long)ws_end);
+    if (d.nrows > *max_rows) *max_rows = d.nrows;
+  }
+  return D2R_OK;
+}
+
+}  // namespace
+
+extern "C" size_t d2r_clip_preprocess_ws_bytes(const d2r_clip_image_desc* h_desc, int B, int S) {
+  int64_t end = 0;
+  for (int b = 0; h_desc && b < B; ++b) {
+    const int64_t e = h_desc[b].ws_offset + (int64_t)h_desc[b].nrows * S * 3;
+    if (e > end) end = e;
+  }
+  return (size_t)end;
+}
+
+extern "C" int d2r_clip_preprocess(const uint8_t* src, int64_t src_bytes, const d2r_clip_image_desc* h_desc,
+                                   const d2r_clip_image_desc* desc, int B, int S, const int32_t* h_tab, const int32_t* tab,
+                                   int64_t tab_len, const float* lut, float* out, void* ws, size_t ws_bytes, void* stream) {
+  D2R_REQUIRE(src && h_desc && desc && h_tab && tab && lut && out && ws, "d2r_clip_preprocess: null pointer");
+  D2R_REQUIRE(B >= 1 && B <= 65535 && S >= 1 && S <= 4096 && tab_len >= 0 && tab_len <= INT32_MAX,
+              "d2r_clip_preprocess: bad batch %d, crop size %d or table length %lld", B, S, (long long)tab_len);
+  D2R_REQUIRE((reinterpret_cast<uintptr_t>(desc) & 7u) == 0 && (reinterpret_cast<uintptr_t>(tab) & 3u) == 0 &&
+                  (reinterpret_cast<uintptr_t>(lut) & 3u) == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0,
+              "d2r_clip_preprocess: desc must be 8-byte, tab / lut / out 4-byte aligned");
+  int max_rows = 0;
+  if (int rc = check_descs(h_desc, B, S, src_bytes, h_tab, tab_len, ws_bytes, &max_rows)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(clip_hpass_kernel, dim3(d2r_cdiv(max_rows, HROWS), B), dim3(256), 0, st, src, desc, tab, S, (uint8_t*)ws);
+  if (int rc = d2r_check_launch("d2r_clip_preprocess (horizontal pass)")) return rc;
+  hipLaunchKernelGGL(clip_vpass_kernel, dim3(d2r_cdiv((int64_t)S * S, 256), B), dim3(256), 0, st, desc, tab, (const uint8_t*)ws, lut,
+                     S, out);
+  return d2r_check_launch("d2r_clip_preprocess (vertical pass)");
+}

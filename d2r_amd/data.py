@@ -1,12 +1,67 @@
-"""Synthetic counterpart of the reference's data layer (processor/dataset.py:50-102): a map-style dataset that emits
-the same 6-tuple ``(input_ids, input_mask, segment_ids, img_mask, label, image)`` with the same dtypes/shapes, and
-a pinned-memory prefetching loader.  The real MVSA/HFM JSON+JPEG pipeline needs the HF tokenizer / CLIP processor
-files and the datasets, which are not available offline; the model/trainer are agnostic to
-where the 6-tuple comes from."""
+"""The data layer of the reference (processor/dataset.py:17-102) and a synthetic counterpart.
+
+``MSDDataset`` reads the MVSA / HFM JSON + JPEG files with the reference's semantics and emits the 6-tuple
+``(input_ids, input_mask, segment_ids, img_mask, label, image)``; its image is the DECODED uint8 RGB array, and ``ClipCollate``
+(d2r_amd.image) packs a batch of them for the CLIP preprocessing kernel, which the trainer runs on the device.
+``SyntheticMSDDataset`` emits the same tuple with a ready fp32 image.  Both go through the pinned-memory prefetching loader."""
 from __future__ import annotations
 
+import json
+import logging
+import os
+
+import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
+
+logger = logging.getLogger(__name__)
+
+
+class MSDDataset(Dataset):
+    """One split of an MVSA / HFM dataset (processor/dataset.py:17-102): `json_path` holds a list of {id, text, emotion_label},
+    the image of sample `id` is ``<img_path>/<id>.jpg``.  Text: ``[CLS] + tokenize(text)[:max_seq - 2] + [SEP]`` as ids, zero
+    padded to max_seq, mask 1 on the tokens, segment ids all 0; img_mask is 50 ones (unused by the model).  The image is opened
+    with PIL and converted to RGB here (in the loader workers) and returned as a uint8 [H, W, 3] array; an image that cannot be
+    opened is replaced by ``<img_path>/inf.png``, as in the reference, and counted.  `tokenizer` is a BertTokenizer or the
+    directory / name to load one from (``do_lower_case=True``)."""
+
+    def __init__(self, json_path: str, img_path: str, tokenizer, max_seq: int = 128):
+        if isinstance(tokenizer, str):
+            from transformers import BertTokenizer
+            tokenizer = BertTokenizer.from_pretrained(tokenizer, do_lower_case=True)
+        self.tokenizer, self.img_path, self.max_seq = tokenizer, img_path, max_seq
+        with open(json_path, "r", encoding="utf-8") as f:
+            data = json.load(f)
+        self.texts = [s["text"] for s in data]
+        self.labels = [int(s["emotion_label"]) for s in data]
+        self.imgs = [str(s["id"]) + ".jpg" for s in data]
+        self.fallbacks = 0
+        logger.info("loaded %d samples from %s", len(data), json_path)
+
+    def __len__(self):
+        return len(self.texts)
+
+    def encode(self, text: str):
+        tokens = ["[CLS]"] + self.tokenizer.tokenize(text)[:self.max_seq - 2] + ["[SEP]"]
+        ids = self.tokenizer.convert_tokens_to_ids(tokens)
+        pad = self.max_seq - len(ids)
+        return (torch.tensor(ids + [0] * pad), torch.tensor([1] * len(ids) + [0] * pad), torch.zeros(self.max_seq, dtype=torch.long))
+
+    def load_image(self, name: str) -> np.ndarray:
+        from PIL import Image
+        try:
+            with Image.open(os.path.join(self.img_path, name)) as im:
+                return np.asarray(im.convert("RGB"))
+        except Exception as e:  # the reference's bare `except:` (processor/dataset.py:91-95)
+            self.fallbacks += 1
+            logger.warning("image %s could not be read (%s): using inf.png (%d fallbacks in this process)", name, e, self.fallbacks)
+            with Image.open(os.path.join(self.img_path, "inf.png")) as im:
+                return np.asarray(im.convert("RGB"))
+
+    def __getitem__(self, idx):
+        ids, mask, seg = self.encode(self.texts[idx])
+        img_mask = torch.ones(50, dtype=torch.long)
+        return ids, mask, seg, img_mask, torch.tensor(self.labels[idx]), self.load_image(self.imgs[idx])
 
 
 class SyntheticMSDDataset(Dataset):
@@ -42,8 +97,8 @@ class SyntheticMSDDataset(Dataset):
 
 
 def make_loader(ds: Dataset, batch_size: int, shuffle: bool, num_workers: int = 0, drop_last: bool = False,
-                sampler=None) -> DataLoader:
+                sampler=None, collate_fn=None) -> DataLoader:
     """pin_memory + (optionally) worker processes, as run.py:131-140; H2D copies are issued non_blocking by the trainer."""
     return DataLoader(ds, batch_size=batch_size, shuffle=shuffle and sampler is None, num_workers=num_workers,
                       pin_memory=torch.cuda.is_available(), drop_last=drop_last, sampler=sampler,
-                      persistent_workers=num_workers > 0)
+                      persistent_workers=num_workers > 0, collate_fn=collate_fn)

@@ -1,0 +1,287 @@
+"""CLIP image preprocessing on the device: what ``CLIPProcessor(images=img)`` does per sample in the reference's loader
+workers (processor/dataset.py:87-95), bit-identical, as one batched launch pair (``d2r_clip_preprocess``, csrc/image.hip).
+
+The processor (transformers' CLIPImageProcessor, PIL backend, with the CLIP defaults) does four things to a uint8 RGB image:
+  1. output size: the short side becomes R (``size["shortest_edge"]``), the long side ``int(R * long / short)``;
+  2. ``PIL.Image.resize(..., BICUBIC)``: Pillow's separable antialiased resampler in 22-bit fixed point, horizontal pass first
+     into a uint8 image, vertical pass from it;
+  3. center crop S x S at ``((rh - S) // 2, (rw - S) // 2)``;
+  4. rescale and normalise: ``(float32(float64(v) * rescale) - float32(mean_c)) / float32(std_c)`` in fp32, a function of the
+     uint8 value and the channel alone (a [3, 256] table).
+The device computes only the cropped pixels (every output pixel depends on its own weights alone), in integer arithmetic.  The
+weights themselves are computed here in float64, in Pillow's operation order (a sequential sum for the normalisation, no fused
+multiply-add): a pairwise sum, or the same arithmetic contracted to FMA on the device, can flip an integer weight.
+
+The loader side (``ClipCollate``) packs a batch of decoded images into ``PackedImages``: one uint8 buffer of the pixels and one
+buffer of descriptors + weight tables; ``PackedImages.to_pixel_values(device)`` copies both (non-blocking from pinned memory) and
+launches the kernels on the current stream.  ``reference_preprocess`` is the same computation in numpy (tests, CPU checks).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+import json
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)  # OpenAI CLIP (CLIPImageProcessor defaults)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+RESCALE = 1 / 255
+PRECISION_BITS = 22  # Pillow's fixed-point weights (libImaging/Resample.c)
+
+DESC_DTYPE = np.dtype([("src_offset", "<i8")] + [(n, "<i4") for n in ("H", "W", "rh", "rw", "top", "left", "kx", "ky", "bx", "cx",
+                                                                      "by", "cy", "row0", "nrows")] + [("ws_offset", "<i8")])
+assert DESC_DTYPE.itemsize == C.sizeof(_lib.ClipImageDesc)
+
+
+def resize_shape(H: int, W: int, R: int):
+    """(rh, rw) of the resize to shortest edge R: Python float division, then truncation (transformers'
+    get_resize_output_image_size with default_to_square=False)."""
+    short, long = (W, H) if W <= H else (H, W)
+    new_long = int(R * long / short)
+    return (new_long, R) if W <= H else (R, new_long)
+
+
+def crop_origin(rh: int, rw: int, S: int):
+    if S > rh or S > rw:
+        raise ValueError(f"a {S} x {S} crop of a {rh} x {rw} image needs padding, which is not supported")
+    return (rh - S) // 2, (rw - S) // 2
+
+
+def _bicubic(x):
+    """Pillow's bicubic filter (a = -0.5), elementwise in float64 with the same operations as the C code."""
+    a = -0.5
+    x = np.abs(x)
+    inner = ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    outer = (((x - 5) * x + 8) * x - 4) * a
+    return np.where(x < 1.0, inner, np.where(x < 2.0, outer, 0.0))
+
+
+@functools.lru_cache(maxsize=4096)
+def bicubic_weights(in_size: int, out_size: int, lo: int, count: int):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for output indices [lo, lo + count) of an in_size -> out_size
+    resize: (bounds int32 [count, 2] = (xmin, n), weights int32 [count, k]); weights past n are 0."""
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = 2.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(lo, lo + count, dtype=np.float64) + 0.5) * scale
+    ss = 1.0 / filterscale
+    xmin = np.maximum(np.trunc(center - support + 0.5), 0).astype(np.int64)
+    n = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), in_size) - xmin
+    x = np.arange(ksize, dtype=np.int64)
+    w = _bicubic(((x[None, :] + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss)
+    w = np.where(x[None, :] < n[:, None], w, 0.0)
+    total = np.add.accumulate(w, axis=1)[:, -1]  # left-to-right, as the C loop (np.sum would be pairwise)
+    w = np.where(total[:, None] != 0.0, w / np.where(total == 0.0, 1.0, total)[:, None], w)
+    one = float(1 << PRECISION_BITS)
+    k = np.where(w < 0, np.trunc(-0.5 + w * one), np.trunc(0.5 + w * one)).astype(np.int32)
+    bounds = np.stack([xmin, n], axis=1).astype(np.int32)
+    bounds.flags.writeable = False
+    k.flags.writeable = False
+    return bounds, k
+
+
+def _clip8(acc):
+    return np.where(acc >= (1 << PRECISION_BITS << 8), 255, np.where(acc <= 0, 0, acc >> PRECISION_BITS)).astype(np.uint8)
+
+
+def _apply(src, bounds, k, axis):
+    """One fixed-point pass along `axis` (1 = columns, 0 = rows) of a uint8 [rows, cols, 3] array."""
+    src = src.astype(np.int64)
+    size = src.shape[axis]
+    acc = np.full((src.shape[0], len(bounds), 3) if axis == 1 else (len(bounds), src.shape[1], 3), 1 << (PRECISION_BITS - 1), np.int64)
+    for t in range(k.shape[1]):
+        idx = np.minimum(bounds[:, 0] + t, size - 1)  # weights past n are 0: the clamped index adds nothing
+        if axis == 1:
+            acc += src[:, idx, :] * k[None, :, t, None]
+        else:
+            acc += src[idx, :, :] * k[:, t, None, None]
+    return _clip8(acc)
+
+
+def resample(img: np.ndarray, rh: int, rw: int, top: int = 0, left: int = 0, h: int = None, w: int = None) -> np.ndarray:
+    """Rows [top, top + h) x columns [left, left + w) of Pillow's BICUBIC resize of uint8 HWC RGB `img` to rh x rw (numpy)."""
+    H, W, _ = img.shape
+    h, w = rh if h is None else h, rw if w is None else w
+    bx, kx = bicubic_weights(W, rw, left, w)
+    by, ky = bicubic_weights(H, rh, top, h)
+    row0, row1 = int(by[0, 0]), int(by[-1, 0] + by[-1, 1])
+    mid = _apply(img[row0:row1], bx, kx, axis=1)
+    return _apply(mid, np.stack([by[:, 0] - row0, by[:, 1]], 1), ky, axis=0)
+
+
+def normalize_table(mean=CLIP_MEAN, std=CLIP_STD, rescale=RESCALE) -> np.ndarray:
+    """fp32 [3, 256]: the normalised value of every (channel, uint8) pair, in the processor's exact arithmetic."""
+    r = (np.arange(256, dtype=np.float64) * float(rescale)).astype(np.float32)
+    m = np.asarray(mean, np.float64).astype(np.float32)[:, None]
+    s = np.asarray(std, np.float64).astype(np.float32)[:, None]
+    return ((r[None, :] - m) / s).astype(np.float32)
+
+
+def reference_preprocess(img: np.ndarray, R: int, S: int, table: np.ndarray = None):
+    """CPU restatement of the whole pipeline: (uint8 crop [S, S, 3], fp32 pixel values [3, S, S])."""
+    rh, rw = resize_shape(img.shape[0], img.shape[1], R)
+    top, left = crop_origin(rh, rw, S)
+    crop = resample(np.ascontiguousarray(img), rh, rw, top, left, S, S)
+    table = normalize_table() if table is None else table
+    return crop, np.stack([table[c][crop[:, :, c]] for c in range(3)])
+
+
+def as_rgb_array(img) -> np.ndarray:
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"expected a uint8 [H, W, 3] RGB image, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def plan_batch(images, R: int, S: int):
+    """Packs decoded images for d2r_clip_preprocess: (pixels uint8 [N], descriptors DESC_DTYPE [B], table int32 [T])."""
+    images = [as_rgb_array(im) for im in images]
+    B = len(images)
+    if B == 0:
+        raise ValueError("empty batch")
+    desc = np.zeros(B, DESC_DTYPE)
+    parts, tab, tlen, src, ws = [], [], 0, 0, 0
+    for b, im in enumerate(images):
+        H, W, _ = im.shape
+        rh, rw = resize_shape(H, W, R)
+        top, left = crop_origin(rh, rw, S)
+        bx, kx = bicubic_weights(W, rw, left, S)
+        by, ky = bicubic_weights(H, rh, top, S)
+        row0, row1 = int(by[0, 0]), int(by[-1, 0] + by[-1, 1])
+        d = desc[b]
+        d["src_offset"], d["H"], d["W"], d["rh"], d["rw"], d["top"], d["left"] = src, H, W, rh, rw, top, left
+        d["kx"], d["ky"], d["row0"], d["nrows"], d["ws_offset"] = kx.shape[1], ky.shape[1], row0, row1 - row0, ws
+        for name, arr in (("bx", bx), ("cx", kx), ("by", by), ("cy", ky)):
+            d[name] = tlen
+            tab.append(arr.reshape(-1))
+            tlen += arr.size
+        parts.append(im.reshape(-1))
+        src += im.size
+        ws += -(-(row1 - row0) * S * 3 // 16) * 16  # 16-byte aligned regions
+    return np.concatenate(parts), desc, np.concatenate(tab).astype(np.int32)
+
+
+@functools.lru_cache(maxsize=16)
+def _device_table(device: str, norm: tuple):
+    return torch.from_numpy(normalize_table(*norm)).to(device)
+
+
+def clip_preprocess(pixels: torch.Tensor, h_desc: np.ndarray, desc: torch.Tensor, h_tab: torch.Tensor, tab: torch.Tensor, S: int,
+                    lut: torch.Tensor, out: torch.Tensor = None, ws: torch.Tensor = None) -> torch.Tensor:
+    """d2r_clip_preprocess on the current stream.  pixels / desc / tab / lut live on the device, h_desc / h_tab are their host
+    copies (the library checks every bound on them before it enqueues anything).  Returns out, fp32 [B, 3, S, S]."""
+    B = len(h_desc)
+    dev = pixels.device
+    if not (pixels.dtype == torch.uint8 and desc.dtype == torch.uint8 and tab.dtype == torch.int32 and lut.dtype == torch.float32):
+        raise TypeError("pixels / desc uint8, tab int32, lut float32 expected")
+    if h_desc.dtype != DESC_DTYPE or desc.numel() != B * DESC_DTYPE.itemsize or h_tab.numel() != tab.numel() or lut.numel() != 768:
+        raise ValueError("descriptor / table / lut sizes disagree")
+    if not all(t.is_cuda and t.device == dev and t.is_contiguous() for t in (desc, tab, lut)) or h_tab.is_cuda or not h_tab.is_contiguous():
+        raise ValueError("device tensors must be contiguous on one GPU, h_tab on the host")
+    hd = C.cast(h_desc.ctypes.data, C.POINTER(_lib.ClipImageDesc))
+    need = int(_lib.load().d2r_clip_preprocess_ws_bytes(hd, B, S))
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * 3 * S * S:
+        raise ValueError("out must be a contiguous fp32 [B, 3, S, S] tensor")
+    from .functional import _stream
+    _lib.call("d2r_clip_preprocess", pixels.data_ptr(), pixels.numel(), hd, desc.data_ptr(), B, S, h_tab.data_ptr(), tab.data_ptr(),
+              tab.numel(), lut.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return out
+
+
+class PackedImages:
+    """A collated batch of decoded images: the loader element the trainer turns into pixel values on the device.
+    ``pixels`` uint8 [N] (HWC RGB images back to back), ``meta`` uint8 [B * 72 + 4 * T] (descriptors, then the int32 table)."""
+
+    def __init__(self, pixels: torch.Tensor, meta: torch.Tensor, batch: int, S: int, norm: tuple):
+        self.pixels, self.meta, self.batch, self.S, self.norm = pixels, meta, batch, S, norm
+
+    @classmethod
+    def from_images(cls, images, R: int, S: int, mean=CLIP_MEAN, std=CLIP_STD, rescale=RESCALE):
+        pixels, desc, tab = plan_batch(images, R, S)
+        meta = np.concatenate([desc.view(np.uint8), tab.view(np.uint8)])
+        return cls(torch.from_numpy(pixels), torch.from_numpy(meta), len(desc),
+                   S, (tuple(float(v) for v in mean), tuple(float(v) for v in std), float(rescale)))
+
+    def __len__(self):
+        return self.batch
+
+    def pin_memory(self, device=None):  # DataLoader(pin_memory=True) calls this in its pinning thread
+        return PackedImages(self.pixels.pin_memory(), self.meta.pin_memory(), self.batch, self.S, self.norm)
+
+    def host_parts(self):
+        nd = self.batch * DESC_DTYPE.itemsize
+        h = self.meta.numpy()
+        return h[:nd].view(DESC_DTYPE), self.meta[nd:].view(torch.int32)
+
+    def to_pixel_values(self, device) -> torch.Tensor:
+        """fp32 [B, 3, S, S] on `device`: the two host-to-device copies (non-blocking; from pinned memory they overlap what the
+        stream is doing) and the two kernels, all on the current stream."""
+        h_desc, h_tab = self.host_parts()
+        pixels = self.pixels.to(device, non_blocking=True)
+        meta = self.meta.to(device, non_blocking=True)
+        nd = self.batch * DESC_DTYPE.itemsize
+        return clip_preprocess(pixels, h_desc, meta[:nd], h_tab, meta[nd:].view(torch.int32), self.S,
+                               _device_table(str(pixels.device), self.norm))
+
+    def to_pixel_values_cpu(self) -> torch.Tensor:
+        """The same batch through the numpy restatement (reference_preprocess): fp32 [B, 3, S, S] on the host."""
+        h_desc, _ = self.host_parts()
+        px = self.pixels.numpy()
+        table = normalize_table(*self.norm)
+        out = []
+        for d in h_desc:
+            img = px[int(d["src_offset"]):int(d["src_offset"]) + int(d["H"]) * int(d["W"]) * 3].reshape(int(d["H"]), int(d["W"]), 3)
+            crop = resample(img, int(d["rh"]), int(d["rw"]), int(d["top"]), int(d["left"]), self.S, self.S)
+            out.append(np.stack([table[c][crop[:, :, c]] for c in range(3)]))
+        return torch.from_numpy(np.stack(out))
+
+
+class ClipCollate:
+    """collate_fn for MSDDataset samples (ids, mask, segments, img_mask, label, uint8 image): the five tensors stacked, the
+    images packed into one PackedImages.  Runs in the loader workers (picklable)."""
+
+    def __init__(self, R: int = 224, S: int = 224, mean=CLIP_MEAN, std=CLIP_STD, rescale=RESCALE):
+        self.R, self.S, self.mean, self.std, self.rescale = R, S, tuple(mean), tuple(std), rescale
+
+    def __call__(self, samples):
+        cols = list(zip(*samples))
+        head = [torch.stack(list(c)) for c in cols[:5]]
+        return (*head, PackedImages.from_images(cols[5], self.R, self.S, self.mean, self.std, self.rescale))
+
+
+def processor_settings(directory: str):
+    """(R, S, mean, std, rescale) from a CLIP checkpoint's preprocessor_config.json.  Only what the device path reproduces
+    exactly is accepted: bicubic resample, resize to a shortest edge, center crop, rescale, normalise, convert to RGB."""
+    path = os.path.join(directory, "preprocessor_config.json")
+    with open(path) as f:
+        cfg = json.load(f)
+    expect = {"do_resize": True, "do_center_crop": True, "do_rescale": True, "do_normalize": True, "do_convert_rgb": True,
+              "resample": 3}
+    for key, want in expect.items():
+        if key in cfg and cfg[key] != want:
+            raise ValueError(f"{path}: {key} = {cfg[key]!r} is not supported (only {want!r}: bicubic CLIP preprocessing)")
+    size, crop = cfg.get("size", 224), cfg.get("crop_size", 224)
+    if isinstance(size, dict):
+        if set(k for k, v in size.items() if v is not None) != {"shortest_edge"}:
+            raise ValueError(f"{path}: size {size} is not supported (only a shortest_edge resize)")
+        size = size["shortest_edge"]
+    if isinstance(crop, dict):
+        if crop.get("height") != crop.get("width"):
+            raise ValueError(f"{path}: only square crops are supported, got {crop}")
+        crop = crop["height"]
+    R, S = int(size), int(crop)
+    if S > R:
+        raise ValueError(f"{path}: a crop of {S} from a shortest edge of {R} needs padding, which is not supported")
+    return (R, S, tuple(cfg.get("image_mean", CLIP_MEAN)), tuple(cfg.get("image_std", CLIP_STD)),
+            float(cfg.get("rescale_factor", RESCALE)))

@@ -1,8 +1,12 @@
 """CLI counterpart of the reference's run.py (run.py:38-158): same flag names and defaults for everything the
 model/trainer consume, plus the extensions of this build (--dtype, --num_classes, --synthetic sizes, data parallel via
-torch.distributed.run).  Data is synthetic (the HF hub files and the MVSA/HFM datasets are not available offline):
+torch.distributed.run).  Without --data_path the data is synthetic; with it, an MVSA / HFM directory is read
+(MSDDataset) and the CLIP image preprocessing runs on the GPU (d2r_amd.image); --pretrained loads the BERT / CLIP checkpoints
+of --bert_name / --vit_name (local directories) as the reference does (run.py:122-153):
 
     python -m d2r_amd.run --num_epochs 2 --batch_size 32 --train_samples 256
+    python -m d2r_amd.run --data_path data/MVSA-single/10-flod-1 --img_path data/MVSA-single/MVSA_Single/data \
+        --bert_name ./bert-base-uncased --vit_name ./clip-vit-base-patch32 --pretrained
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m d2r_amd.run --batch_size 256
 """
 from __future__ import annotations
@@ -87,13 +91,41 @@ def build_parser():
     p.add_argument("--dp_exact", action="store_true", help="data parallelism: BatchNorm statistics of the GLAC cells, the [B,B] similarity "
                    "matrices and the JS loss over the GLOBAL batch (the reference's single-GPU semantics) instead of per rank")
     p.add_argument("--cleanup_output", action="store_true", help="reference behaviour: rmtree('./output') at the end")
+    p.add_argument("--data_path", default=None, type=str, help="directory with train.json, dev.json (or HFM's valid.json) and "
+                   "test.json; without it the data is synthetic")
+    p.add_argument("--img_path", default=None, type=str, help="directory of the <id>.jpg images (and inf.png) of --data_path")
+    p.add_argument("--pretrained", action="store_true", help="model configs, weights and image preprocessing from the local "
+                   "--bert_name / --vit_name checkpoints (BertModel, CLIPModel.vision_model, preprocessor_config.json)")
     return p
+
+
+def dataset_files(data_path: str):
+    """(train, dev, test) JSON files of an MVSA / HFM directory: dev.json, or HFM's valid.json."""
+    dev = os.path.join(data_path, "dev.json")
+    if not os.path.exists(dev):
+        dev = os.path.join(data_path, "valid.json")
+    files = (os.path.join(data_path, "train.json"), dev, os.path.join(data_path, "test.json"))
+    missing = [f for f in files if not os.path.exists(f)]
+    if missing:
+        raise SystemExit(f"--data_path {data_path}: missing {', '.join(missing)}")
+    return files
+
+
+def load_pretrained(args):
+    """(text_config, vision_config, clip_vision_state_dict, bert_state_dict) from the local checkpoints (run.py:122-153)."""
+    from transformers import BertConfig, BertModel, CLIPConfig, CLIPModel
+    text_config = BertConfig.from_pretrained(args.bert_name)
+    vision_config = CLIPConfig.from_pretrained(args.vit_name).vision_config
+    clip_sd = CLIPModel.from_pretrained(args.vit_name).vision_model.state_dict()
+    bert_sd = BertModel.from_pretrained(args.bert_name).state_dict()
+    return text_config, vision_config, clip_sd, bert_sd
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     from .config import TextConfig, VisionConfig
-    from .data import SyntheticMSDDataset, make_loader
+    from .data import MSDDataset, SyntheticMSDDataset, make_loader
+    from .image import CLIP_MEAN, CLIP_STD, RESCALE, ClipCollate, processor_settings
     from .dp import init_process_group_from_env
     from .modules import UnimoModelF
     from .train import MSDTrainer
@@ -109,24 +141,43 @@ def main(argv=None):
     if args.batch_size % world:
         raise SystemExit(f"--batch_size {args.batch_size} must be divisible by the world size {world}")
     per_rank = args.batch_size // world
+    clip_sd = bert_sd = None
+    if args.pretrained:
+        text_config, vision_config, clip_sd, bert_sd = load_pretrained(args)
+        R, S, mean, std, rescale = processor_settings(args.vit_name)
+        if S != vision_config.image_size:
+            raise SystemExit(f"{args.vit_name}: the processor crops {S} x {S} but the vision model takes {vision_config.image_size}")
+        args.image_size, args.patch_size = vision_config.image_size, vision_config.patch_size
+    else:
+        text_config = TextConfig(num_hidden_layers=args.encoder_layers, hidden_dropout_prob=args.bert_dropout,
+                                 attention_probs_dropout_prob=args.bert_dropout)
+        vision_config = VisionConfig(num_hidden_layers=args.encoder_layers, image_size=args.image_size, patch_size=args.patch_size)
+        R, S, mean, std, rescale = args.image_size, args.image_size, CLIP_MEAN, CLIP_STD, RESCALE
     ntok = (args.image_size // args.patch_size) ** 2 + 1
+    if args.data_path is not None:
+        if args.img_path is None:
+            raise SystemExit("--data_path needs --img_path")
+        files = dataset_files(args.data_path)
+        collate = ClipCollate(R, S, mean, std, rescale)
 
-    def loader(n, seed, shuffle):
-        ds = SyntheticMSDDataset(n, args.max_seq, args.image_size, args.num_classes, seed=seed, num_image_tokens=ntok)
+    def loader(n, seed, shuffle, split):
+        if args.data_path is None:
+            ds = SyntheticMSDDataset(n, args.max_seq, args.image_size, args.num_classes, seed=seed, num_image_tokens=ntok)
+        else:
+            ds = MSDDataset(files[split], args.img_path, args.bert_name, args.max_seq)
         sampler = None
         if world > 1 and shuffle:  # only the TRAINING set is sharded; every rank evaluates the whole dev / test set
             sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=shuffle,
                                                                       seed=args.seed)
-        return make_loader(ds, per_rank, shuffle, args.num_workers, drop_last=shuffle, sampler=sampler)
+        return make_loader(ds, per_rank, shuffle, args.num_workers, drop_last=shuffle, sampler=sampler,
+                           collate_fn=None if args.data_path is None else collate)
 
-    train_dl, dev_dl, test_dl = loader(args.train_samples, 1, True), loader(args.eval_samples, 2, False), loader(args.eval_samples, 3, False)
-    text_config = TextConfig(num_hidden_layers=args.encoder_layers, hidden_dropout_prob=args.bert_dropout,
-                             attention_probs_dropout_prob=args.bert_dropout)
-    vision_config = VisionConfig(num_hidden_layers=args.encoder_layers, image_size=args.image_size, patch_size=args.patch_size)
+    train_dl, dev_dl = loader(args.train_samples, 1, True, 0), loader(args.eval_samples, 2, False, 1)
+    test_dl = loader(args.eval_samples, 3, False, 2)
     model = UnimoModelF(args=args, vision_config=vision_config, text_config=text_config, num_classes=args.num_classes)
     trainer = MSDTrainer(train_data=train_dl, dev_data=dev_dl, test_data=test_dl, model=model, args=args, logger=logger,
                          writer=None)
-    trainer.train(None, None)  # pretrained CLIP/BERT dicts are unavailable offline; ingest is exercised in tests
+    trainer.train(clip_sd, bert_sd)  # None, None without --pretrained: randomly initialised encoders
     if trainer.samples_per_sec:
         logger.info("training throughput: %.1f samples/s on %d GPU(s)", trainer.samples_per_sec, world)
 

@@ -22,6 +22,7 @@ import torch
 
 from . import functional as F
 from .dp import DataParallel
+from .image import PackedImages
 from .params import FusedAdamW, LinearWarmupSchedule, ParamStore
 
 
@@ -106,7 +107,9 @@ class MSDTrainer:
         self.logger.info("Load model successful!")
 
     def _to_device(self, batch):
-        return tuple(t.to(self.args.device, non_blocking=True) if isinstance(t, torch.Tensor) else t for t in batch)
+        # tensors are copied; a batch of decoded images (MSDDataset + ClipCollate) becomes its CLIP pixel values on the device
+        return tuple(t.to(self.args.device, non_blocking=True) if isinstance(t, torch.Tensor) else
+                     t.to_pixel_values(self.args.device) if isinstance(t, PackedImages) else t for t in batch)
 
     # -- training (modules/train.py:77-159) -----------------------------------------------------------
     def train(self, clip_model_dict=None, bert_model_dict=None):

@@ -555,6 +555,33 @@ int d2r_bert_embed_bwd(int dtype, const void* dY, const int64_t* ids, const int6
                        int ntype, int64_t pad_id, float* dword, float* dpos, float* dtype_tab, void* stream);
 /* im2col for the stride=kernel patch conv: pixels fp32 [B,3,H,W] -> patches T [B*(H/p)*(W/p), 3*p*p] */
 int d2r_patchify(int dtype, const float* pixels, int B, int H, int W, int p, void* patches, void* stream);
+/* CLIP image preprocessing of a batch of decoded images (processor/dataset.py:87-95: CLIPProcessor(images=...) per sample,
+ * with resample=BICUBIC, size={"shortest_edge": R}, crop_size=S x S): Pillow's antialiased fixed-point bicubic resize, the center
+ * crop, the rescale and the normalisation, bit-identical to the CPU processor.  Only the cropped pixels are computed.
+ *   src   : packed uint8 HWC RGB images, image i at byte src_offset (H x W x 3, rows contiguous); src_bytes bounds them all;
+ *   tab   : int32 table of the resampler, built on the host in float64 (Pillow's operation order): per crop column j of image i,
+ *           the pair (xmin, n) at tab[bx + 2j] and n <= kx fixed-point (22-bit) weights at tab[cx + j*kx]; likewise per crop row
+ *           (ymin, n) at tab[by + 2i] and weights at tab[cy + i*ky];
+ *   lut   : fp32 [3, 256]: the normalised value of every (channel, uint8) pair;
+ *   out   : fp32 [B, 3, S, S] (what d2r_patchify consumes), OVERWRITTEN;
+ *   ws    : the uint8 rows of the horizontal pass, >= d2r_clip_preprocess_ws_bytes(); image i owns [ws_offset, ws_offset +
+ *           nrows * S * 3), regions in image order and disjoint.
+ * h_desc / h_tab are host copies of desc / tab: every bound is checked on them before anything is enqueued, and a refused call
+ * (D2R_ERR_INVALID / D2R_ERR_WORKSPACE) writes nothing.  A crop larger than the resized image is refused (no padding). */
+typedef struct {
+  int64_t src_offset;  /* byte offset of the image in src */
+  int H, W;            /* source rows, columns */
+  int rh, rw;          /* size after the resize */
+  int top, left;       /* crop origin in the resized image */
+  int kx, ky;          /* weights per crop column / row (row stride in tab) */
+  int bx, cx, by, cy;  /* int32 offsets into tab (see above) */
+  int row0, nrows;     /* source rows [row0, row0 + nrows) the horizontal pass covers (every crop row's support) */
+  int64_t ws_offset;   /* byte offset of the image's intermediate rows in ws */
+} d2r_clip_image_desc;
+size_t d2r_clip_preprocess_ws_bytes(const d2r_clip_image_desc* h_desc, int B, int S);
+int d2r_clip_preprocess(const uint8_t* src, int64_t src_bytes, const d2r_clip_image_desc* h_desc, const d2r_clip_image_desc* desc,
+                        int B, int S, const int32_t* h_tab, const int32_t* tab, int64_t tab_len, const float* lut, float* out,
+                        void* ws, size_t ws_bytes, void* stream);
 /* x[b,0,:] = cls + pos[0]; x[b,1+i,:] = patch_emb[b,i,:] + pos[1+i]  (in place on x [B,1+np,D], rows 1.. already
  * hold the patch GEMM output) */
 int d2r_clip_embed_finish(int dtype, void* x, const float* cls, const float* pos, int B, int ntok, int D,
