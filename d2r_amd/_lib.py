@@ -86,6 +86,16 @@ class ClipImageDesc(C.Structure):
                                                           "row0", "nrows")] + [("ws_offset", i64)]
 
 
+class JpegImageDesc(C.Structure):
+    _fields_ = [(n, i64) for n in ("dst_offset", "ws_rec", "ws_coef", "ws_plane")] + \
+        [(n, i32) for n in ("H", "W", "ncomp", "hs", "vs", "fancy", "mcux", "mcuy", "mcu_blocks", "restart", "seg0", "nseg", "nchunk")] + \
+        [(n, i32 * 3) for n in ("h", "v", "bw", "bh", "qt", "dc", "ac")] + [("mcu_map", i32 * 10)]
+
+
+class JpegSegment(C.Structure):
+    _fields_ = [("offset", i64), ("bits", i32), ("chunk0", i32)]
+
+
 # name -> (restype, argtypes); every symbol include/d2r_hip.h declares
 SIGNATURES = {
     "d2r_head_arena_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
@@ -175,6 +185,9 @@ SIGNATURES = {
     "d2r_patchify": (i32, [i32, vp, i32, i32, i32, i32, vp, vp]),
     "d2r_clip_preprocess_ws_bytes": (sz, [C.POINTER(ClipImageDesc), i32, i32]),
     "d2r_clip_preprocess": (i32, [vp, i64, C.POINTER(ClipImageDesc), vp, i32, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
+    "d2r_jpeg_decode_ws_bytes": (sz, [C.POINTER(JpegImageDesc), i32]),
+    "d2r_jpeg_decode": (i32, [vp, i64, C.POINTER(JpegImageDesc), vp, i32, C.POINTER(JpegSegment), vp, i32, vp, vp, i64,
+                              vp, i64, vp, vp, vp, sz, vp]),
     "d2r_clip_embed_finish": (i32, [i32, vp, vp, vp, i32, i32, i32, vp]),
     "d2r_clip_embed_bwd": (i32, [i32, vp, i32, i32, i32, vp, vp, vp]),
     "d2r_adamw_step": (i32, [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, i64, f32, vp, vp]),

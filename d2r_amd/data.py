@@ -6,6 +6,7 @@
 ``SyntheticMSDDataset`` emits the same tuple with a ready fp32 image.  Both go through the pinned-memory prefetching loader."""
 from __future__ import annotations
 
+import io
 import json
 import logging
 import os
@@ -13,6 +14,8 @@ import os
 import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
+
+from .jpeg import route
 
 logger = logging.getLogger(__name__)
 
@@ -23,9 +26,14 @@ class MSDDataset(Dataset):
     padded to max_seq, mask 1 on the tokens, segment ids all 0; img_mask is 50 ones (unused by the model).  The image is opened
     with PIL and converted to RGB here (in the loader workers) and returned as a uint8 [H, W, 3] array; an image that cannot be
     opened is replaced by ``<img_path>/inf.png``, as in the reference, and counted.  `tokenizer` is a BertTokenizer or the
-    directory / name to load one from (``do_lower_case=True``)."""
+    directory / name to load one from (``do_lower_case=True``).  With ``image_decode="device"`` the workers only read the file:
+    a JPEG that d2r_amd.jpeg.parse accepts is returned parsed (a JpegInfo, decoded on the GPU with the batch), any other file
+    is decoded here as above."""
 
-    def __init__(self, json_path: str, img_path: str, tokenizer, max_seq: int = 128):
+    def __init__(self, json_path: str, img_path: str, tokenizer, max_seq: int = 128, image_decode: str = "host"):
+        if image_decode not in ("host", "device"):
+            raise ValueError(f"image_decode must be 'host' or 'device', got {image_decode!r}")
+        self.image_decode = image_decode
         if isinstance(tokenizer, str):
             from transformers import BertTokenizer
             tokenizer = BertTokenizer.from_pretrained(tokenizer, do_lower_case=True)
@@ -47,9 +55,17 @@ class MSDDataset(Dataset):
         pad = self.max_seq - len(ids)
         return (torch.tensor(ids + [0] * pad), torch.tensor([1] * len(ids) + [0] * pad), torch.zeros(self.max_seq, dtype=torch.long))
 
-    def load_image(self, name: str) -> np.ndarray:
+    def load_image(self, name: str):
         from PIL import Image
         try:
+            if self.image_decode == "device":
+                with open(os.path.join(self.img_path, name), "rb") as f:
+                    data = f.read()
+                info, _ = route(data)
+                if info is not None:
+                    return info
+                with Image.open(io.BytesIO(data)) as im:
+                    return np.asarray(im.convert("RGB"))
             with Image.open(os.path.join(self.img_path, name)) as im:
                 return np.asarray(im.convert("RGB"))
         except Exception as e:  # the reference's bare `except:` (processor/dataset.py:91-95)

@@ -143,29 +143,36 @@ def as_rgb_array(img) -> np.ndarray:
 def plan_batch(images, R: int, S: int):
     """Packs decoded images for d2r_clip_preprocess: (pixels uint8 [N], descriptors DESC_DTYPE [B], table int32 [T])."""
     images = [as_rgb_array(im) for im in images]
-    B = len(images)
+    if not images:
+        raise ValueError("empty batch")
+    offsets = np.cumsum([0] + [im.size for im in images[:-1]])
+    desc, tab = plan_layout([im.shape[:2] for im in images], offsets, R, S)
+    return np.concatenate([im.reshape(-1) for im in images]), desc, tab
+
+
+def plan_layout(shapes, offsets, R: int, S: int):
+    """Descriptors DESC_DTYPE [B] and the int32 table for images of `shapes` (H, W) whose pixels sit at byte `offsets` of the
+    source buffer (the images need not be decoded yet)."""
+    B = len(shapes)
     if B == 0:
         raise ValueError("empty batch")
     desc = np.zeros(B, DESC_DTYPE)
-    parts, tab, tlen, src, ws = [], [], 0, 0, 0
-    for b, im in enumerate(images):
-        H, W, _ = im.shape
+    tab, tlen, ws = [], 0, 0
+    for b, (H, W) in enumerate(shapes):
         rh, rw = resize_shape(H, W, R)
         top, left = crop_origin(rh, rw, S)
         bx, kx = bicubic_weights(W, rw, left, S)
         by, ky = bicubic_weights(H, rh, top, S)
         row0, row1 = int(by[0, 0]), int(by[-1, 0] + by[-1, 1])
         d = desc[b]
-        d["src_offset"], d["H"], d["W"], d["rh"], d["rw"], d["top"], d["left"] = src, H, W, rh, rw, top, left
+        d["src_offset"], d["H"], d["W"], d["rh"], d["rw"], d["top"], d["left"] = int(offsets[b]), H, W, rh, rw, top, left
         d["kx"], d["ky"], d["row0"], d["nrows"], d["ws_offset"] = kx.shape[1], ky.shape[1], row0, row1 - row0, ws
         for name, arr in (("bx", bx), ("cx", kx), ("by", by), ("cy", ky)):
             d[name] = tlen
             tab.append(arr.reshape(-1))
             tlen += arr.size
-        parts.append(im.reshape(-1))
-        src += im.size
         ws += -(-(row1 - row0) * S * 3 // 16) * 16  # 16-byte aligned regions
-    return np.concatenate(parts), desc, np.concatenate(tab).astype(np.int32)
+    return desc, np.concatenate(tab).astype(np.int32)
 
 
 @functools.lru_cache(maxsize=16)
@@ -249,14 +256,22 @@ class PackedImages:
 
 class ClipCollate:
     """collate_fn for MSDDataset samples (ids, mask, segments, img_mask, label, uint8 image): the five tensors stacked, the
-    images packed into one PackedImages.  Runs in the loader workers (picklable)."""
+    images packed into one PackedImages.  Runs in the loader workers (picklable).  With ``image_decode="device"`` (for
+    MSDDataset(image_decode="device")), or when some images are parsed JPEG files, the batch becomes a
+    d2r_amd.jpeg.PackedJpegImages, which decodes those on the device."""
 
-    def __init__(self, R: int = 224, S: int = 224, mean=CLIP_MEAN, std=CLIP_STD, rescale=RESCALE):
+    def __init__(self, R: int = 224, S: int = 224, mean=CLIP_MEAN, std=CLIP_STD, rescale=RESCALE, image_decode: str = "host"):
         self.R, self.S, self.mean, self.std, self.rescale = R, S, tuple(mean), tuple(std), rescale
+        self.image_decode = image_decode
 
     def __call__(self, samples):
         cols = list(zip(*samples))
         head = [torch.stack(list(c)) for c in cols[:5]]
+        from .jpeg import JpegInfo, PackedJpegImages
+        if self.image_decode == "device" or any(isinstance(im, JpegInfo) for im in cols[5]):
+            # MSDDataset(image_decode="device"): parsed JPEG files for the device, any others decoded; every such batch is a
+            # PackedJpegImages, so that the trainer counts its host-decoded images too
+            return (*head, PackedJpegImages.from_items(cols[5], self.R, self.S, self.mean, self.std, self.rescale))
         return (*head, PackedImages.from_images(cols[5], self.R, self.S, self.mean, self.std, self.rescale))
 
 

@@ -94,6 +94,9 @@ def build_parser():
     p.add_argument("--data_path", default=None, type=str, help="directory with train.json, dev.json (or HFM's valid.json) and "
                    "test.json; without it the data is synthetic")
     p.add_argument("--img_path", default=None, type=str, help="directory of the <id>.jpg images (and inf.png) of --data_path")
+    p.add_argument("--image_decode", default="host", choices=["host", "device"], help="with --data_path: decode the JPEG files in "
+                   "the loader workers with Pillow (host), or only parse them there and decode them on the GPU, bit-identically "
+                   "(device; files the device path does not take, e.g. progressive JPEGs, are still decoded on the host)")
     p.add_argument("--pretrained", action="store_true", help="model configs, weights and image preprocessing from the local "
                    "--bert_name / --vit_name checkpoints (BertModel, CLIPModel.vision_model, preprocessor_config.json)")
     return p
@@ -158,13 +161,13 @@ def main(argv=None):
         if args.img_path is None:
             raise SystemExit("--data_path needs --img_path")
         files = dataset_files(args.data_path)
-        collate = ClipCollate(R, S, mean, std, rescale)
+        collate = ClipCollate(R, S, mean, std, rescale, image_decode=args.image_decode)
 
     def loader(n, seed, shuffle, split):
         if args.data_path is None:
             ds = SyntheticMSDDataset(n, args.max_seq, args.image_size, args.num_classes, seed=seed, num_image_tokens=ntok)
         else:
-            ds = MSDDataset(files[split], args.img_path, args.bert_name, args.max_seq)
+            ds = MSDDataset(files[split], args.img_path, args.bert_name, args.max_seq, image_decode=args.image_decode)
         sampler = None
         if world > 1 and shuffle:  # only the TRAINING set is sharded; every rank evaluates the whole dev / test set
             sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=shuffle,

@@ -22,7 +22,7 @@ import torch
 
 from . import functional as F
 from .dp import DataParallel
-from .image import PackedImages
+from .jpeg import DecodeLog
 from .params import FusedAdamW, LinearWarmupSchedule, ParamStore
 
 
@@ -70,6 +70,7 @@ class MSDTrainer:
         self.writer = writer
         self.step = 0
         self.refresh_step = 2
+        self.decode_log = DecodeLog(self.logger)  # --image_decode device: device / host split and decode status per epoch
         self.best_dev_metric = 0
         self.best_dev_epoch = None
         self.optimizer = None
@@ -107,9 +108,10 @@ class MSDTrainer:
         self.logger.info("Load model successful!")
 
     def _to_device(self, batch):
-        # tensors are copied; a batch of decoded images (MSDDataset + ClipCollate) becomes its CLIP pixel values on the device
+        # tensors are copied; a packed batch of images (MSDDataset + ClipCollate: PackedImages, or PackedJpegImages with
+        # image_decode="device") becomes its CLIP pixel values on the device
         return tuple(t.to(self.args.device, non_blocking=True) if isinstance(t, torch.Tensor) else
-                     t.to_pixel_values(self.args.device) if isinstance(t, PackedImages) else t for t in batch)
+                     t.to_pixel_values(self.args.device) if hasattr(t, "to_pixel_values") else t for t in batch)
 
     # -- training (modules/train.py:77-159) -----------------------------------------------------------
     def train(self, clip_model_dict=None, bert_model_dict=None):
@@ -141,7 +143,8 @@ class MSDTrainer:
                 self.step += 1
                 if self.step == warm + 1 and t_mark is None:
                     t_mark = time.time()
-                batch = self._to_device(batch)
+                packed, batch = batch, self._to_device(batch)
+                self.decode_log.note(packed)
                 self.dp.begin_step()
                 (loss, logits), labels = self._step(batch, mode="train")
                 F._lib.call("d2r_axpby", F.F32, 1.0, loss.detach().data_ptr(), 1.0, run_loss.data_ptr(), 1, F._stream())
@@ -156,11 +159,13 @@ class MSDTrainer:
                 if self.step % self.refresh_step == 0:
                     avg_loss = float(run_loss.item()) / self.refresh_step  # the only host sync of the loop
                     run_loss.zero_()
+                    self.decode_log.poll()  # decode status of the batches so far: complete after the sync above
                     if t_mark is not None and seen:
                         self.samples_per_sec = seen / max(t_train + time.time() - t_mark, 1e-9)
                     self.logger.info("step %d loss:%-6.5f samples/s:%.1f", self.step, avg_loss, self.samples_per_sec or 0.0)
                     if self.writer:
                         self.writer.add_scalar(tag="train_loss", scalar_value=avg_loss, global_step=self.step)
+            self.decode_log.end_epoch(epoch)
             if t_mark is not None:
                 if self.args.device != "cpu" and torch.cuda.is_available():
                     torch.cuda.synchronize()

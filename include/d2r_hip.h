@@ -582,6 +582,64 @@ size_t d2r_clip_preprocess_ws_bytes(const d2r_clip_image_desc* h_desc, int B, in
 int d2r_clip_preprocess(const uint8_t* src, int64_t src_bytes, const d2r_clip_image_desc* h_desc, const d2r_clip_image_desc* desc,
                         int B, int S, const int32_t* h_tab, const int32_t* tab, int64_t tab_len, const float* lut, float* out,
                         void* ws, size_t ws_bytes, void* stream);
+/* K19  Baseline JPEG decoding of a batch of images on the device (processor/dataset.py:89: Image.open(p).convert("RGB") in the
+ * reference's loader workers), bit-identical to libjpeg-turbo's default path as Pillow uses it: Huffman decoding, ISLOW IDCT with
+ * its range-limit table, fancy h2v1 / h2v2 chroma upsampling, fixed-point YCbCr -> RGB.  The host (d2r_amd/jpeg.py) parses the
+ * markers, removes byte stuffing and splits the scan at RSTn markers; what it accepts (SOF0 / SOF1, 8-bit, one scan, grayscale or
+ * YCbCr at 4:4:4 / 4:2:2 / 4:2:0, optional restart interval) is decoded here.
+ *   data  : the unstuffed restart segments, segment s at byte seg[s].offset (4-byte aligned), seg[s].bits bits, followed by at least
+ *           D2R_JPEG_SEG_PAD zero bytes inside data_bytes;
+ *   seg   : image i owns segments [seg0, seg0 + nseg), one per restart interval (nseg == 1 without one); chunk0 numbers the
+ *           D2R_JPEG_CHUNK_BITS-bit chunks of the image's segments consecutively (at least one per segment), nchunk in all;
+ *   tab   : int32 tables: per component c a 64-entry quantisation table (natural order) at tab[qt[c]], the DC and AC Huffman decode
+ *           tables (D2R_JPEG_HUFF_INTS each: look[512] = (length << 8) | symbol for codes of at most 9 bits, maxcode[17],
+ *           valoff[17], vals[256]) at tab[dc[c]] and tab[ac[c]];
+ *   dst   : image i's uint8 HWC RGB pixels are written to [dst_offset, dst_offset + H * W * 3) (what d2r_clip_preprocess reads);
+ *           regions in image order and disjoint;
+ *   status: int32 [B], OVERWRITTEN: 0, or an OR of D2R_JPEG_BAD_CODE (no Huffman code matches), D2R_JPEG_SHORT (a segment's data
+ *           ends before its last block; the blocks it does not reach stay zero), D2R_JPEG_BAD_RUN (a run of coefficients past the
+ *           64th; decoded as libjpeg does).  A bad code reads as symbol 0 after 17 bits and decoding goes on; such an image's pixels
+ *           need not match libjpeg's warn-and-continue output.  The other images of the batch are unaffected;
+ *   stats : optional int32 [B, 2], OVERWRITTEN: the most synchronisation rounds any workgroup of the image took, and the chunks the
+ *           cross-workgroup pass decoded again;
+ *   ws    : >= d2r_jpeg_decode_ws_bytes(); image i owns 48 * nchunk bytes at ws_rec (chunk states), 128 bytes per block at ws_coef
+ *           (coefficients) and 64 bytes per block at ws_plane (component samples); all ws_rec regions come first, then all ws_coef,
+ *           then all ws_plane, each kind in image order, 256-byte aligned and disjoint.
+ * h_desc / h_seg / h_tab are host copies of desc / seg / tab: every offset, size, table index and segment bound is checked on them
+ * before anything is enqueued, and a refused call (D2R_ERR_INVALID / D2R_ERR_WORKSPACE) writes nothing.  No host read-back: the
+ * entropy decode synchronises its chunks on the device (see csrc/jpeg.hip). */
+#define D2R_JPEG_CHUNK_BITS 1024
+#define D2R_JPEG_SEG_PAD 8
+#define D2R_JPEG_HUFF_INTS 802
+#define D2R_JPEG_BAD_CODE 1
+#define D2R_JPEG_SHORT 2
+#define D2R_JPEG_BAD_RUN 4
+typedef struct {
+  int64_t dst_offset;                /* byte offset of the image's HWC pixels in dst */
+  int64_t ws_rec, ws_coef, ws_plane; /* byte offsets of the image's workspace regions */
+  int H, W;
+  int ncomp;                         /* 1 (grayscale, written as R = G = B) or 3 (YCbCr) */
+  int hs, vs;                        /* chroma upsampling ratio: (1, 1), (2, 1) or (2, 2) */
+  int fancy;                         /* libjpeg's fancy upsampling (chroma planes wider than 2 samples) */
+  int mcux, mcuy;                    /* MCUs per row / column */
+  int mcu_blocks;                    /* blocks per MCU (1 for grayscale) */
+  int restart;                       /* restart interval in MCUs, 0 = none */
+  int seg0, nseg, nchunk;            /* segments [seg0, seg0 + nseg) of seg, chunks in all */
+  int h[3], v[3];                    /* blocks of component c per MCU, across and down */
+  int bw[3], bh[3];                  /* blocks of component c per row / column (mcux * h[c], mcuy * v[c]) */
+  int qt[3], dc[3], ac[3];           /* int32 offsets of component c's tables in tab */
+  int mcu_map[10];                   /* block j of an MCU: component | (column in the MCU << 4) | (row in the MCU << 8) */
+} d2r_jpeg_image_desc;
+typedef struct {
+  int64_t offset;  /* byte offset in data */
+  int bits;        /* entropy-coded bits of the segment */
+  int chunk0;      /* the image's chunk index of the segment's first chunk */
+} d2r_jpeg_segment;
+size_t d2r_jpeg_decode_ws_bytes(const d2r_jpeg_image_desc* h_desc, int B);
+int d2r_jpeg_decode(const uint8_t* data, int64_t data_bytes, const d2r_jpeg_image_desc* h_desc, const d2r_jpeg_image_desc* desc, int B,
+                    const d2r_jpeg_segment* h_seg, const d2r_jpeg_segment* seg, int nseg, const int32_t* h_tab, const int32_t* tab,
+                    int64_t tab_len, uint8_t* dst, int64_t dst_bytes, int32_t* status, int32_t* stats, void* ws, size_t ws_bytes,
+                    void* stream);
 /* x[b,0,:] = cls + pos[0]; x[b,1+i,:] = patch_emb[b,i,:] + pos[1+i]  (in place on x [B,1+np,D], rows 1.. already
  * hold the patch GEMM output) */
 int d2r_clip_embed_finish(int dtype, void* x, const float* cls, const float* pos, int B, int ntok, int D,
