@@ -10,10 +10,15 @@ Workload = BASELINE.json configs[1] ("C2"): synthetic MVSA-Single shape — per-
 (BASELINE.md section 3).  Compute dtype of the headline: fp16 (IEEE half MFMA operands and activation storage, fp32
 accumulation / statistics / softmax / poolers / Block / loss, fp32 master weights, dynamic loss scale) — the 16-bit mode
 whose logits and loss stay within the north star's 1e-3 of the reference (asserted in tests/test_gpu_model.py and
-tests/test_gpu_bench_shapes.py; DESIGN.md section 2 shows why no bf16-operand mode can).  The bf16 number is reported
-beside it (`bf16_path`), never as `value`.  Weak scaling: the per-GPU batch is fixed as N grows.
+tests/test_gpu_bench_shapes.py; DESIGN.md section 2 shows why no bf16-operand mode can).  With --full the bf16 number is
+reported beside it (`bf16_path`), never as `value`.  Weak scaling: the per-GPU batch is fixed as N grows.
 
-Extra objects on the JSON line (tier contract section 4):
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line (headline keys plus
+what the timed region itself yields: final_loss, host_enqueue_ms_per_step).  Everything measured after that runs only with
+--full (each leg can still be left out there with its --no-* flag):
+  fwd_bwd_only  a second short timed loop of fwd+bwd without optimiser / all-reduce
+  host_only     the same step at batch 2, where the loop time is the host's enqueue cost
+  fp32_path, bf16_path / fp16_path   the same step in the other compute dtypes (the other 16-bit one in a child process)
   roofline      the dominant kernel family by GPU time, timed live with HIP events on the launching stream in an
                 instrumented pass of the SAME step right after the timed region (per-launch events would perturb
                 the timed region); `roofline_kernels` lists router pool (K1), route_aggregate (K8) and the
@@ -68,6 +73,9 @@ def parse():
     ap.add_argument("--classes", type=int, default=3, help="classes of the head (3 = MVSA; BASELINE configs[3], TumEmo: 7)")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16", "f32"],
                     help="compute dtype; fp16 (default) is the 16-bit mode that meets the 1e-3 logits/loss tolerance")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs below (fwd+bwd only, host cost, other dtypes, roofline, CPU baseline); "
+                         "a plain run measures only the headline")
     ap.add_argument("--no-alt-leg", "--no-fp16-leg", dest="no_alt_leg", action="store_true",
                     help="skip the number of the OTHER 16-bit compute dtype reported beside the headline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -246,7 +254,7 @@ def main():
                     attention_probs_dropout_prob=args.bert_dropout)
     vc = VisionConfig(num_hidden_layers=args.layers, image_size=args.image_size, patch_size=args.patch)
     model = M.UnimoModelF(default_args(DR_step=args.dr_step, num_cells=args.num_cells), vc, tc, num_classes=args.classes)
-    sd_cpu = {k: v.detach().clone() for k, v in model.state_dict().items()} if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    sd_cpu = {k: v.detach().clone() for k, v in model.state_dict().items()} if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None
     log("model built on host")
     model.to(dev).set_compute_dtype(dtype).train()
     store = ParamStore(model, dtype)
@@ -350,32 +358,11 @@ def main():
         dumped = dump_outputs(args.dump_outputs, loss, static["logits"] if args.graph else last["logits"], store, opt)
         log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
 
-    # From here on no rank issues a gradient collective any more (the legs below are local measurements; rank 0 runs
-    # one more pass than the others): switch the overlap hooks off on every rank.
-    dp.overlap = False
-
-    # SURVEY.md 8d also asks for fwd+bwd WITHOUT the optimiser: a short second timed loop (not `value`)
-    def fwd_bwd_only():
-        dp.begin_step()
-        loss, _ = model(*batch)
-        opt.backward(loss)
-        opt.zero_grad()
-
-    n2 = max(3, args.steps // 2)
-    fwd_bwd_only()
-    fence()
-    t1 = time.perf_counter()
-    for _ in range(n2):
-        fwd_bwd_only()
-    fence()
-    fb_ms = (time.perf_counter() - t1) / n2 * 1e3
-    log(f"fwd+bwd without optimiser / all-reduce: {fb_ms:.2f} ms/step")
-
     out = {
         "metric": "samples/sec fwd+bwd", "value": round(value, 2), "unit": "samples/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "precision": PRECISION_NOTE[args.dtype], "data": "synthetic",
-        "headline_dtype_history": "value is the fp16 compute mode since round 3 (BENCH_r01 / r02: bf16); the bf16 mode of this build is bf16_path",
+        "headline_dtype_history": "value is the fp16 compute mode since round 3 (BENCH_r01 / r02: bf16); the bf16 mode of this build is bf16_path (--full)",
         "config": {"workload": "%s: synthetic MVSA-Single-style batch, per-GPU batch %d, seq_len %d, %d image tokens, "
                                "DR_step %d, %d cells per routing layer, %d classes, %d+%d encoder layers, random-init weights, dropout %g; "
                                "step = fwd+bwd+grad-allreduce+AdamW"
@@ -385,11 +372,33 @@ def main():
         "final_loss": round(loss_val, 5), "launch": "hipGraph replay" if args.graph else "eager",
         "host_enqueue_ms_per_step": round(host_ms, 3),
         "dump_outputs": {"dir": args.dump_outputs, "arrays": dumped} if dumped is not None else None,
-        "fwd_bwd_only": {"ms_per_step_per_rank": round(fb_ms, 3), "samples_per_s": round(world * args.batch / fb_ms * 1e3, 2),
-                         "note": "no optimiser step, no gradient all-reduce; measured on rank 0's clock"},
     }
 
-    if rank == 0 and world == 1 and not args.graph and not args.no_host_leg:
+    if args.full:
+        # From here on no rank issues a gradient collective any more (the legs below are local measurements; rank 0 runs
+        # one more pass than the others): switch the overlap hooks off on every rank.
+        dp.overlap = False
+
+        # SURVEY.md 8d also asks for fwd+bwd WITHOUT the optimiser: a short second timed loop (not `value`)
+        def fwd_bwd_only():
+            dp.begin_step()
+            loss, _ = model(*batch)
+            opt.backward(loss)
+            opt.zero_grad()
+
+        n2 = max(3, args.steps // 2)
+        fwd_bwd_only()
+        fence()
+        t1 = time.perf_counter()
+        for _ in range(n2):
+            fwd_bwd_only()
+        fence()
+        fb_ms = (time.perf_counter() - t1) / n2 * 1e3
+        log(f"fwd+bwd without optimiser / all-reduce: {fb_ms:.2f} ms/step")
+        out["fwd_bwd_only"] = {"ms_per_step_per_rank": round(fb_ms, 3), "samples_per_s": round(world * args.batch / fb_ms * 1e3, 2),
+                               "note": "no optimiser step, no gradient all-reduce; measured on rank 0's clock"}
+
+    if args.full and rank == 0 and world == 1 and not args.graph and not args.no_host_leg:
         # What the HOST needs to enqueue one step, separated from the GPU: the same model and step at batch 2 - the GPU drains its
         # queue long before the host refills it, so the loop time is host time (launch calls, autograd, Python).  The
         # host_enqueue figure above is taken at the benchmark batch, where the host mostly waits for room in the launch queue.
@@ -417,7 +426,7 @@ def main():
             out["host_only_ms_per_step"] = None
             out["host_only_note"] = repr(e)
 
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         # Per-kernel durations: the same step, but launched op by op on ONE stream (whole-layer C calls and the
         # two-stream overlap switched off), so that every launch is bracketed by its own pair of HIP events and runs
         # alone on the GPU — the durations rocprofv3 --kernel-trace reports (it serialises dispatches too).
@@ -570,7 +579,7 @@ def main():
         out["roofline_kernels"] = top + [e for e in kernels[20:] if e["kernel"].startswith(named)]
         out["kernel_ms_per_step_total"] = round(total_ms, 3)
 
-    if rank == 0 and world == 1 and args.dtype != "f32" and not args.no_fp32_leg:
+    if args.full and rank == 0 and world == 1 and args.dtype != "f32" and not args.no_fp32_leg:
         # The same step on the fp32 HIP path (exact-f32 MFMA, the parity reference: logits within 1e-7 of the reference),
         # reported NEXT to the headline so that the price of the 16-bit compute dtype is visible; never `value`.
         try:
@@ -591,17 +600,15 @@ def main():
         finally:
             model.set_compute_dtype(dtype)
 
-    if rank == 0 and world == 1 and args.dtype in ("fp16", "bf16") and not args.no_alt_leg and not args.graph:
+    if args.full and rank == 0 and world == 1 and args.dtype in ("fp16", "bf16") and not args.no_alt_leg and not args.graph:
         # The same step with the OTHER 16-bit compute dtype (same kernels and MFMA rate; bf16: 8 significant bits and no loss
-        # scale, fp16: 11 bits and a scaled loss).  Run as a child process (its own ParamStore and 16-bit shadow); never `value`.
+        # scale, fp16: 11 bits and a scaled loss).  Run as a plain child run (its own ParamStore and 16-bit shadow); never `value`.
         alt = "bf16" if args.dtype == "fp16" else "fp16"
         try:
             import subprocess
             cmd = [sys.executable, os.path.abspath(__file__), "--dtype", alt, "--steps", str(min(args.steps, 10)), "--warmup", "3",
                    "--batch", str(args.batch), "--seq", str(args.seq), "--layers", str(args.layers), "--image-size", str(args.image_size),
-                   "--patch", str(args.patch), "--dr-step", str(args.dr_step), "--num-cells", str(args.num_cells), "--classes", str(args.classes),
-                   "--no-cpu-baseline",
-                   "--no-fp32-leg", "--no-roofline", "--no-alt-leg", "--no-host-leg"]
+                   "--patch", str(args.patch), "--dr-step", str(args.dr_step), "--num-cells", str(args.num_cells), "--classes", str(args.classes)]
             torch.cuda.synchronize()
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Aggregates the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; separate runs, as the counters do not fit one
-pass on gfx950) of `bench.py --steps 2 --warmup 1` into per-kernel-family HBM traffic per d2r_gemm launch.
+pass on gfx950) of `bench.py --full --steps 2 --warmup 1` into per-kernel-family HBM traffic per d2r_gemm launch.
 
   python profiles/make_pmc_summary.py gpurun_out/pmc/fetch/f_counter_collection.csv \
          gpurun_out/pmc/write/w_counter_collection.csv profiles/pmc_traffic_r01.json
@@ -115,9 +115,9 @@ def load(path, counter):
 
 fetch, n_f = load(sys.argv[1], "FETCH_SIZE")
 write, n_w = load(sys.argv[2], "WRITE_SIZE")
-# steps of the profiled command: 1 warm-up + 2 timed + 4 of the fwd+bwd-only leg (bench.py --steps 2 --warmup 1) = 7
+# steps of the profiled command: 1 warm-up + 2 timed + 4 of the fwd+bwd-only leg (bench.py --full --steps 2 --warmup 1) = 7
 STEPS = int(sys.argv[4]) if len(sys.argv) > 4 else 7
-out = {"_doc": "HBM bytes from rocprofv3 --pmc (FETCH_SIZE x2 on gfx950, WRITE_SIZE exact); bench.py --steps 2 --warmup 1, C2 "
+out = {"_doc": "HBM bytes from rocprofv3 --pmc (FETCH_SIZE x2 on gfx950, WRITE_SIZE exact); bench.py --full --steps 2 --warmup 1, C2 "
                "workload (%d steps in the run).  *_per_launch: per GEMM kernel of the REAL step (a grouped weight-gradient launch "
                "holds 6-16 problems); hbm_bytes_per_step: family total per training step - bench.py divides it by the launches "
                "per step of its per-kernel pass to compare with the algorithmic bytes per launch." % STEPS,

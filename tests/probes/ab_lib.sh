@@ -1,5 +1,5 @@
 # A/B of two builds of the library on ONE box: $1 = the other build (a copy of libd2r_hip.so); alternates new / old twice
-F="--steps 40 --warmup 6 --no-cpu-baseline --no-fp32-leg --no-alt-leg --no-host-leg --no-roofline"
+F="--steps 40 --warmup 6 --full --no-cpu-baseline --no-fp32-leg --no-alt-leg --no-host-leg --no-roofline"
 cp d2r_amd/libd2r_hip.so /tmp/lib_new.so
 run() { timeout -k 10 200 python bench.py $F 2>/dev/null | python -c "
 import json,sys

@@ -6,7 +6,7 @@
 set -o pipefail
 OUT=$GRAFT_REPO_ROOT/gpurun_out/${1:-prof}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && mkdir -p $OUT
-FLAGS="--no-cpu-baseline --no-roofline --no-fp32-leg --no-alt-leg --no-host-leg"
+FLAGS="--full --no-cpu-baseline --no-roofline --no-fp32-leg --no-alt-leg --no-host-leg"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py --steps 6 --warmup 2 $FLAGS > $OUT/kt.log 2>&1 || exit 11
 cp $(find $OUT/kt -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv
 python3 profiles/make_step_gaps.py $(find $OUT/kt -name "*kernel_trace.csv" | head -1) $OUT/step_gaps.json > $OUT/step_gaps.log 2>&1 || exit 16
@@ -30,6 +30,6 @@ timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv 
 python3 profiles/make_pmc_summary.py $(find $OUT/fetch -name "*counter_collection.csv" | head -1) $(find $OUT/write -name "*counter_collection.csv" | head -1) $OUT/pmc_traffic.json > $OUT/pmc_summary.log 2>&1 || exit 14
 rm -rf $OUT/fetch $OUT/write
 echo "[collect] counter passes done"
-timeout -k 10 500 python3 bench.py > $OUT/bench.log 2> $OUT/bench.err || exit 15
+timeout -k 10 500 python3 bench.py --full > $OUT/bench.log 2> $OUT/bench.err || exit 15
 tail -1 $OUT/bench.log > $OUT/bench.json
 ls -la $OUT
