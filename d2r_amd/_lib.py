@@ -178,6 +178,7 @@ SIGNATURES = {
     "d2r_jsdiv_bwd": (i32, [vp, vp, i32, vp, vp, vp, vp]),
     "d2r_ce_fwd": (i32, [vp, vp, i32, i32, vp, vp]),
     "d2r_ce_bwd": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+    "d2r_argmax_rows": (i32, [vp, i64, i64, i32, vp, vp]),
     "d2r_block_merge_fwd": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "d2r_block_merge_bwd": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "d2r_bert_embed_fwd": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),

@@ -944,7 +944,8 @@ extern "C" size_t d2r_head_bwd_scratch(int B, int E, int mm, int chunks, int ran
 extern "C" int d2r_head_fwd(const d2r_head_desc* D, void* stream) {
   HeadDims h;
   TRY(head_dims(D, h));
-  D2R_REQUIRE(D->x0 && D->x1 && D->labels && D->js && D->loss && D->logits && D->pooled && D->arena, "d2r_head_fwd: null pointer");
+  D2R_REQUIRE(D->x0 && D->x1 && D->logits && D->pooled && D->arena, "d2r_head_fwd: null pointer");
+  D2R_REQUIRE(!D->labels || (D->js && D->loss), "d2r_head_fwd: labels given without js / loss");
   D2R_REQUIRE(D->arena_bytes >= d2r_head_arena_bytes(h.B, h.E, h.mm, h.chunks, h.rank, h.classes), "d2r_head_fwd: arena too small");
   const Ctx c{D2R_F32, stream, D->splitk_ws, D->splitk_bytes};
   Arena A(D->arena);
@@ -957,6 +958,7 @@ extern "C" int d2r_head_fwd(const d2r_head_desc* D, void* stream) {
   TRY(d2r_block_merge_fwd(D2R_F32, a.m0, a.m1, h.B, h.chunks, h.rank, h.size, a.z, a.zraw, stream));
   TRY(lin(c, h.B, h.E, h.mm, a.z, h.mm, D->lin_out, D->pooled));
   TRY(lin(c, h.B, h.classes, h.E, D->pooled, h.E, D->fc, D->logits));
+  if (!D->labels) return D2R_OK;  // prediction: logits and pooled only
   TRY(d2r_ce_fwd(D->logits, D->labels, h.B, h.classes, a.ce, stream));
   const float* xs[2] = {a.ce, D->js};
   const float coef[2] = {1.f, 1.f};
@@ -966,7 +968,8 @@ extern "C" int d2r_head_fwd(const d2r_head_desc* D, void* stream) {
 extern "C" int d2r_head_bwd(const d2r_head_desc* D, void* stream) {
   HeadDims h;
   TRY(head_dims(D, h));
-  D2R_REQUIRE(D->x0 && D->x1 && D->labels && D->logits && D->pooled && D->arena && D->d_loss && D->d_x0 && D->d_x1 && D->d_js && D->scratch,
+  D2R_REQUIRE(D->labels, "d2r_head_bwd: labels are required (a label-free forward has no loss to differentiate)");
+  D2R_REQUIRE(D->x0 && D->x1 && D->logits && D->pooled && D->arena && D->d_loss && D->d_x0 && D->d_x1 && D->d_js && D->scratch,
               "d2r_head_bwd: null pointer");
   D2R_REQUIRE(D->scratch_bytes >= d2r_head_bwd_scratch(h.B, h.E, h.mm, h.chunks, h.rank, h.classes), "d2r_head_bwd: scratch too small");
   for (const d2r_linear_params* p : {&D->lin0, &D->lin1, &D->merge0, &D->merge1, &D->lin_out, &D->fc})

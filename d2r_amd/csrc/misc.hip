@@ -405,6 +405,39 @@ extern "C" int d2r_ce_bwd(const float* logits, const int64_t* labels, int B, int
 }
 
 // =====================================================================================================
+// argmax over the last dim (logits.argmax(-1) at modules/train.py:181,243): thread per row, torch.argmax's rules
+// =====================================================================================================
+__global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ X, int64_t ld, int64_t rows, int cols,
+                                                          int64_t* __restrict__ idx) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
+    const float* x = X + r * ld;
+    float best = x[0];
+    int bi = 0;
+    if (!__builtin_isnan(best)) {
+      for (int c = 1; c < cols; ++c) {
+        const float v = x[c];
+        if (__builtin_isnan(v)) {  // a NaN is the maximum; the first one wins
+          bi = c;
+          break;
+        }
+        if (v > best) best = v, bi = c;  // strict: a tie keeps the lower index
+      }
+    }
+    idx[r] = bi;
+  }
+}
+extern "C" int d2r_argmax_rows(const float* X, int64_t ld, int64_t rows, int cols, int64_t* idx, void* stream) {
+  D2R_REQUIRE(rows >= 0 && cols >= 1 && ld >= cols, "d2r_argmax_rows: bad shape (rows %lld, cols %d, ld %lld)", (long long)rows, cols,
+              (long long)ld);
+  if (rows == 0) return D2R_OK;
+  D2R_REQUIRE(X && idx, "d2r_argmax_rows: null pointer");
+  const int64_t blocks = (rows + 255) / 256;
+  hipLaunchKernelGGL(argmax_rows_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, X, ld,
+                     rows, cols, idx);
+  return d2r_check_launch("d2r_argmax_rows");
+}
+
+// =====================================================================================================
 // K10 Block merge (models/XModules.py:541-549): wave per (sample, chunk)
 // =====================================================================================================
 template <typename T>

@@ -28,9 +28,11 @@ class MSDDataset(Dataset):
     opened is replaced by ``<img_path>/inf.png``, as in the reference, and counted.  `tokenizer` is a BertTokenizer or the
     directory / name to load one from (``do_lower_case=True``).  With ``image_decode="device"`` the workers only read the file:
     a JPEG that d2r_amd.jpeg.parse accepts is returned parsed (a JpegInfo, decoded on the GPU with the batch), any other file
-    is decoded here as above."""
+    is decoded here as above.  ``labels_optional=True`` (prediction): an entry without ``emotion_label`` gets label -1 instead of
+    raising.  ``ids`` keeps every entry's id, in file order."""
 
-    def __init__(self, json_path: str, img_path: str, tokenizer, max_seq: int = 128, image_decode: str = "host"):
+    def __init__(self, json_path: str, img_path: str, tokenizer, max_seq: int = 128, image_decode: str = "host",
+                 labels_optional: bool = False):
         if image_decode not in ("host", "device"):
             raise ValueError(f"image_decode must be 'host' or 'device', got {image_decode!r}")
         self.image_decode = image_decode
@@ -41,8 +43,12 @@ class MSDDataset(Dataset):
         with open(json_path, "r", encoding="utf-8") as f:
             data = json.load(f)
         self.texts = [s["text"] for s in data]
-        self.labels = [int(s["emotion_label"]) for s in data]
-        self.imgs = [str(s["id"]) + ".jpg" for s in data]
+        if labels_optional:
+            self.labels = [int(s["emotion_label"]) if s.get("emotion_label") is not None else -1 for s in data]
+        else:
+            self.labels = [int(s["emotion_label"]) for s in data]
+        self.ids = [str(s["id"]) for s in data]
+        self.imgs = [i + ".jpg" for i in self.ids]
         self.fallbacks = 0
         logger.info("loaded %d samples from %s", len(data), json_path)
 

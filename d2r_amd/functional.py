@@ -1206,6 +1206,27 @@ class HeadBundle:
         self.key = (w0.data_ptr(), w0._d2r_grad.data_ptr())
 
 
+def _head_fwd(x0, x1, js, labels, bundle: HeadBundle):
+    """One d2r_head_fwd call on contiguous fp32 inputs: -> (loss, logits, pooled, descriptor, arena).  labels=None: the label-free
+    forward (labels, js and loss NULL; loss returned as None) - the same descriptor and launches up to the logits otherwise."""
+    B = x0.shape[0]
+    lib = _lib.load()
+    d = _lib.HeadDesc()
+    d.B, d.E, d.mm, d.chunks, d.rank, d.classes = B, bundle.E, bundle.mm, bundle.chunks, bundle.rank, bundle.classes
+    d.lin0, d.lin1, d.merge0, d.merge1, d.lin_out, d.fc = bundle.lp
+    loss = None if labels is None else torch.empty((), dtype=torch.float32, device=x0.device)
+    logits = torch.empty(B, bundle.classes, dtype=torch.float32, device=x0.device)
+    pooled = torch.empty(B, bundle.E, dtype=torch.float32, device=x0.device)
+    arena = torch.empty(lib.d2r_head_arena_bytes(B, bundle.E, bundle.mm, bundle.chunks, bundle.rank, bundle.classes), dtype=torch.uint8,
+                        device=x0.device)
+    ws = _workspace(64 << 20, x0.device)
+    d.x0, d.x1, d.labels, d.js = x0.data_ptr(), x1.data_ptr(), _ptr(labels), None if labels is None else _ptr(js)
+    d.loss, d.logits, d.pooled = _ptr(loss), logits.data_ptr(), pooled.data_ptr()
+    d.arena, d.arena_bytes, d.splitk_ws, d.splitk_bytes = arena.data_ptr(), arena.numel(), ws.data_ptr(), ws.numel()
+    _lib.call("d2r_head_fwd", C.byref(d), _stream(), meta=dict(group="head_fwd"))
+    return loss, logits, pooled, d, arena
+
+
 class _Head(torch.autograd.Function):
     """(loss, logits, pooled) = head(text_pooled, vision_pooled, js_loss, labels): ONE C call each way.  Only `loss` carries a
     gradient (the end of the training graph); a gradient arriving at logits / pooled is refused."""
@@ -1214,21 +1235,7 @@ class _Head(torch.autograd.Function):
     def forward(ctx, x0, x1, js, labels, anchor, bundle):
         x0, x1, js = x0.contiguous(), x1.contiguous(), js.contiguous()
         labels = labels.contiguous().long()
-        B = x0.shape[0]
-        lib = _lib.load()
-        d = _lib.HeadDesc()
-        d.B, d.E, d.mm, d.chunks, d.rank, d.classes = B, bundle.E, bundle.mm, bundle.chunks, bundle.rank, bundle.classes
-        d.lin0, d.lin1, d.merge0, d.merge1, d.lin_out, d.fc = bundle.lp
-        loss = torch.empty((), dtype=torch.float32, device=x0.device)
-        logits = torch.empty(B, bundle.classes, dtype=torch.float32, device=x0.device)
-        pooled = torch.empty(B, bundle.E, dtype=torch.float32, device=x0.device)
-        arena = torch.empty(lib.d2r_head_arena_bytes(B, bundle.E, bundle.mm, bundle.chunks, bundle.rank, bundle.classes), dtype=torch.uint8,
-                            device=x0.device)
-        ws = _workspace(64 << 20, x0.device)
-        d.x0, d.x1, d.labels, d.js = x0.data_ptr(), x1.data_ptr(), labels.data_ptr(), js.data_ptr()
-        d.loss, d.logits, d.pooled = loss.data_ptr(), logits.data_ptr(), pooled.data_ptr()
-        d.arena, d.arena_bytes, d.splitk_ws, d.splitk_bytes = arena.data_ptr(), arena.numel(), ws.data_ptr(), ws.numel()
-        _lib.call("d2r_head_fwd", C.byref(d), _stream(), meta=dict(group="head_fwd"))
+        loss, logits, pooled, d, arena = _head_fwd(x0, x1, js, labels, bundle)
         ctx.save_for_backward(x0, x1, labels, logits, pooled)
         ctx.d, ctx.keep, ctx.bundle = d, arena, bundle
         ctx.set_materialize_grads(False)
@@ -1264,7 +1271,13 @@ class _Head(torch.autograd.Function):
 
 
 def head(x0, x1, js, labels, bundle: HeadBundle):
-    """Block fusion + fc + cross entropy + (ce + js) as a single autograd node: -> (loss, logits [B, classes], pooled [B, 768])."""
+    """Block fusion + fc + cross entropy + (ce + js) as a single autograd node: -> (loss, logits [B, classes], pooled [B, 768]).
+    labels=None: prediction, -> (None, logits, pooled) from the same launches minus the loss; only outside autograd recording."""
+    if labels is None:
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (x0, x1, *bundle.params)):
+            raise _lib.D2RError("head: a label-free call has no loss to differentiate; call it under torch.no_grad()")
+        _, logits, pooled, _, _ = _head_fwd(x0.contiguous(), x1.contiguous(), None, None, bundle)
+        return None, logits, pooled
     return _Head.apply(x0, x1, js, labels, bundle.params[0], bundle)
 
 
@@ -1364,6 +1377,21 @@ class _SoftmaxRows(torch.autograd.Function):
 
 def softmax_rows(x):
     return _SoftmaxRows.apply(x)
+
+
+def argmax_rows(x):
+    """Predicted class per row of an fp32 [rows, cols] tensor (torch.argmax(-1)'s rules: lowest index on ties, first NaN wins):
+    -> int64 [rows]."""
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise _lib.D2RError("argmax_rows: fp32 [rows, cols] expected")
+    rows, cols = x.shape
+    # rows of `cols` unit-stride elements, `ld` apart and not overlapping (an expanded / overlapping view is refused, not read past)
+    ld = x.stride(0) if rows > 1 else cols
+    if cols > 1 and x.stride(1) != 1 or ld < cols:
+        raise _lib.D2RError(f"argmax_rows: rows must be unit-stride and not overlap (strides {tuple(x.stride())}, shape {tuple(x.shape)})")
+    idx = torch.empty(rows, dtype=torch.int64, device=x.device)
+    _lib.call("d2r_argmax_rows", x.data_ptr(), ld, rows, cols, idx.data_ptr(), _stream())
+    return idx
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -655,8 +655,11 @@ class DecodeLog:
                                     "Pillow would give", n, self.bad)
 
     def end_epoch(self, epoch):
+        self.end_pass("epoch %d" % epoch)
+
+    def end_pass(self, what):
         self.poll()
         if self.device or self.host:
-            self.logger.info("epoch %d images: %d decoded on the device, %d on the host, %d device decode(s) with corrupt data", epoch,
+            self.logger.info("%s images: %d decoded on the device, %d on the host, %d device decode(s) with corrupt data", what,
                              self.device, self.host, self.bad)
         self.device = self.host = self.bad = 0

@@ -514,7 +514,9 @@ class _InteractionBase(D2RModule):
             self._bundle_cache = b
         return b if b.supports(own, other) else None
 
-    def forward(self, text, image):
+    def forward(self, text, image, return_paths=False):
+        """-> ([emb], sim_paths [B_global, B_global]); return_paths: -> ([emb], sim_paths, paths), paths = this rank's fp32 per-sample
+        router outputs [B, nc^2 (DR_step - 1) + nc] before the data-parallel gather (detached; models/InteractionModule.py:23-45)."""
         own, other = (image, text) if self.dynamic_itr_l0.swap else (text, image)
         bundle = self._bundle(own, other)
         if bundle is not None:  # K16: the whole module as one C call per direction
@@ -524,8 +526,9 @@ class _InteractionBase(D2RModule):
                             if "glac" in layer.cell_names]
                 if counters:
                     torch._foreach_add_(counters, 1)  # one launch for the module's counters instead of one each
+            own_paths = paths.detach()
             paths = F.gather_batch(paths)  # (global-batch-exact data parallelism: the paths of every rank's samples)
-            return [out], F.matmul_nt(paths, paths)
+            return ([out], F.matmul_nt(paths, paths), own_paths) if return_paths else ([out], F.matmul_nt(paths, paths))
         B = text.shape[0]
         layers = [self.dynamic_itr_l0, *self.dynamic_itr_l1, self.dynamic_itr_l2]
         kvs = [None] * len(layers)
@@ -540,8 +543,10 @@ class _InteractionBase(D2RModule):
             plist.append(pm.reshape(B, -1))
         out, pf = self.dynamic_itr_l2(refs, text, image, kvs[-1])
         plist.append(pf.reshape(B, -1))
-        paths = F.gather_batch(torch.cat(plist, dim=-1))  # fp32 [B, 36(DR-1)+6]; DR_step=2 (extension): cat(l0, l2)
-        return out, F.matmul_nt(paths, paths)
+        paths = torch.cat(plist, dim=-1)  # fp32 [B, 36(DR-1)+6]; DR_step=2 (extension): cat(l0, l2)
+        own_paths = paths.detach()
+        paths = F.gather_batch(paths)
+        return (out, F.matmul_nt(paths, paths), own_paths) if return_paths else (out, F.matmul_nt(paths, paths))
 
 
 class InteractionModule(_InteractionBase):
@@ -953,23 +958,25 @@ class UnimoModel(D2RModule):
         if not EARLY_SELF_LAYERS:
             t_cls, v_cls = self_layers()
         with on_t():
-            (emb_t,), sim_paths = self.itr_module(t_enc, v_enc)
+            (emb_t,), sim_paths, paths_t = self.itr_module(t_enc, v_enc, return_paths=True)
             t_cls = F.gather_batch(t_cls)  # (global-batch-exact data parallelism: the [B,B] matrices span the global batch)
             js1 = F.js_div(sim_paths, F.matmul_nt(t_cls, t_cls))
             tp = self.text_pool(emb_t, fp32=True)
         with on_v():
-            (emb_v,), rev_sim_paths = self.Reversed_itr_module(t_enc, v_enc)
+            (emb_v,), rev_sim_paths, paths_v = self.Reversed_itr_module(t_enc, v_enc, return_paths=True)
             v_cls = F.gather_batch(v_cls)
             js2 = F.js_div(rev_sim_paths, F.matmul_nt(v_cls, v_cls))
             vp_ = self.vision_pool(emb_v, fp32=True)
         if two:
             main.wait_stream(sT)
             main.wait_stream(sV)
-            for x in (js1, js2, tp, vp_, emb_t, emb_v, sim_paths, rev_sim_paths, t_enc, v_enc):
+            for x in (js1, js2, tp, vp_, emb_t, emb_v, sim_paths, rev_sim_paths, paths_t, paths_v, t_enc, v_enc):
                 x.record_stream(main)
         js_loss = F.lincomb([-self.args.weight_js_1, -self.args.weight_js_2], [js1, js2])
-        aux = dict(emb_text=emb_t, emb_image=emb_v, sim_paths=sim_paths, rev_sim_paths=rev_sim_paths,
-                   text_encode_out=t_enc, vision_encode_out=v_enc, text_pooled=tp, vision_pooled=vp_)
+        # paths_text / paths_image: this rank's fp32 per-sample router outputs [B, nc^2 (DR_step - 1) + nc] (layer 0's [nc, nc]
+        # block, the middle layers' blocks, the final layer's nc gates: models/InteractionModule.py:23-45)
+        aux = dict(emb_text=emb_t, emb_image=emb_v, sim_paths=sim_paths, rev_sim_paths=rev_sim_paths, paths_text=paths_t,
+                   paths_image=paths_v, text_encode_out=t_enc, vision_encode_out=v_enc, text_pooled=tp, vision_pooled=vp_)
         hb = self._head_bundle(head[0]) if head is not None and tp.dtype == torch.float32 and tp.is_cuda else None
         if hb is not None:
             # the one stretch of a step where both branch streams wait for the launching stream: ~35 short launches of the
@@ -981,7 +988,8 @@ class UnimoModel(D2RModule):
 
 
 class UnimoModelF(D2RModule):
-    """Drop-in surface: forward(input_ids, attention_mask, token_type_ids, labels, images) -> (loss, logits)."""
+    """Drop-in surface: forward(input_ids, attention_mask, token_type_ids, labels, images) -> (loss, logits).
+    labels=None (prediction, under torch.no_grad() only): -> (None, logits), the logits bit-identical to a labelled call's."""
 
     def __init__(self, args, vision_config, text_config, num_classes: int = 3):
         super().__init__()
@@ -990,14 +998,18 @@ class UnimoModelF(D2RModule):
         self.fc = Linear(text_config.hidden_size, num_classes)
         self.last_aux = None
 
-    def forward(self, input_ids, attention_mask, token_type_ids, labels, images):
+    def forward(self, input_ids, attention_mask, token_type_ids, labels=None, images=None):
+        if images is None:
+            raise ValueError("images is None")
+        if labels is None and torch.is_grad_enabled():
+            raise RuntimeError("UnimoModelF: a call without labels has no loss to differentiate; predict under torch.no_grad()")
         pooled, js_loss, aux = self.model(input_ids=input_ids, attention_mask=attention_mask,
                                           token_type_ids=token_type_ids, pixel_values=images, head=(self.fc, labels))
         if "loss" in aux:  # Block, fc, cross entropy and the sum were one call inside the model
             loss, logits = aux.pop("loss"), aux.pop("logits")
         else:
             logits = self.fc(pooled, fp32=True)
-            loss = F.lincomb([1.0, 1.0], [F.cross_entropy(logits, labels), js_loss])
+            loss = None if labels is None else F.lincomb([1.0, 1.0], [F.cross_entropy(logits, labels), js_loss])
         aux["js_loss"] = js_loss
         self.last_aux = aux
         return loss, logits

@@ -8,6 +8,9 @@ of --bert_name / --vit_name (local directories) as the reference does (run.py:12
     python -m d2r_amd.run --data_path data/MVSA-single/10-flod-1 --img_path data/MVSA-single/MVSA_Single/data \
         --bert_name ./bert-base-uncased --vit_name ./clip-vit-base-patch32 --pretrained
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m d2r_amd.run --batch_size 256
+
+--only_test --load_path <best_model.pth> predicts the test split with a saved checkpoint (no training; unlabelled test entries
+allowed), --write_path writes the per-sample predictions as JSON Lines (MSDTrainer.predict); both are single-process.
 """
 from __future__ import annotations
 
@@ -45,10 +48,11 @@ def build_parser():
     p.add_argument("--seed", default=2023, type=int)
     p.add_argument("--load_path", default=None, type=str)
     p.add_argument("--save_path", default="./output/", type=str)
-    p.add_argument("--write_path", default=None, type=str)
+    p.add_argument("--write_path", default=None, type=str, help="JSON Lines file of per-sample test-split predictions: the only pass "
+                   "with --only_test, one pass with the best checkpoint after training otherwise")
     p.add_argument("--notes", default="", type=str)
     p.add_argument("--do_train", action="store_true", default=True)
-    p.add_argument("--only_test", action="store_true")
+    p.add_argument("--only_test", action="store_true", help="predict the test split with the --load_path checkpoint, no training")
     p.add_argument("--max_seq", default=128, type=int)
     p.add_argument("--ignore_idx", default=0, type=int)
     p.add_argument("--sample_ratio", default=1.0, type=float)
@@ -114,11 +118,14 @@ def dataset_files(data_path: str):
     return files
 
 
-def load_pretrained(args):
-    """(text_config, vision_config, clip_vision_state_dict, bert_state_dict) from the local checkpoints (run.py:122-153)."""
+def load_pretrained(args, weights: bool = True):
+    """(text_config, vision_config, clip_vision_state_dict, bert_state_dict) from the local checkpoints (run.py:122-153);
+    weights=False: the configs only (None, None for the state dicts)."""
     from transformers import BertConfig, BertModel, CLIPConfig, CLIPModel
     text_config = BertConfig.from_pretrained(args.bert_name)
     vision_config = CLIPConfig.from_pretrained(args.vit_name).vision_config
+    if not weights:
+        return text_config, vision_config, None, None
     clip_sd = CLIPModel.from_pretrained(args.vit_name).vision_model.state_dict()
     bert_sd = BertModel.from_pretrained(args.bert_name).state_dict()
     return text_config, vision_config, clip_sd, bert_sd
@@ -126,6 +133,10 @@ def load_pretrained(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.only_test and args.load_path is None:
+        raise SystemExit("--only_test needs --load_path (the checkpoint to evaluate)")
+    if (args.only_test or args.write_path is not None) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--only_test / --write_path run in a single process: start without torch.distributed.run (WORLD_SIZE 1)")
     from .config import TextConfig, VisionConfig
     from .data import MSDDataset, SyntheticMSDDataset, make_loader
     from .image import CLIP_MEAN, CLIP_STD, RESCALE, ClipCollate, processor_settings
@@ -146,7 +157,8 @@ def main(argv=None):
     per_rank = args.batch_size // world
     clip_sd = bert_sd = None
     if args.pretrained:
-        text_config, vision_config, clip_sd, bert_sd = load_pretrained(args)
+        # --only_test: configs and preprocessing from the local directories, every weight from the checkpoint
+        text_config, vision_config, clip_sd, bert_sd = load_pretrained(args, weights=not args.only_test)
         R, S, mean, std, rescale = processor_settings(args.vit_name)
         if S != vision_config.image_size:
             raise SystemExit(f"{args.vit_name}: the processor crops {S} x {S} but the vision model takes {vision_config.image_size}")
@@ -167,7 +179,8 @@ def main(argv=None):
         if args.data_path is None:
             ds = SyntheticMSDDataset(n, args.max_seq, args.image_size, args.num_classes, seed=seed, num_image_tokens=ntok)
         else:
-            ds = MSDDataset(files[split], args.img_path, args.bert_name, args.max_seq, image_decode=args.image_decode)
+            ds = MSDDataset(files[split], args.img_path, args.bert_name, args.max_seq, image_decode=args.image_decode,
+                            labels_optional=args.only_test and split == 2)  # unlabelled posts: only the test split of --only_test
         sampler = None
         if world > 1 and shuffle:  # only the TRAINING set is sharded; every rank evaluates the whole dev / test set
             sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=shuffle,
@@ -175,14 +188,22 @@ def main(argv=None):
         return make_loader(ds, per_rank, shuffle, args.num_workers, drop_last=shuffle, sampler=sampler,
                            collate_fn=None if args.data_path is None else collate)
 
-    train_dl, dev_dl = loader(args.train_samples, 1, True, 0), loader(args.eval_samples, 2, False, 1)
+    if not args.only_test:
+        train_dl, dev_dl = loader(args.train_samples, 1, True, 0), loader(args.eval_samples, 2, False, 1)
     test_dl = loader(args.eval_samples, 3, False, 2)
     model = UnimoModelF(args=args, vision_config=vision_config, text_config=text_config, num_classes=args.num_classes)
+    if args.only_test:
+        trainer = MSDTrainer(test_data=test_dl, model=model, args=args, logger=logger, writer=None)
+        trainer._load_checkpoint(args.load_path)  # strict: every key of the model, nothing else
+        trainer.predict(test_dl, args.write_path)
+        return
     trainer = MSDTrainer(train_data=train_dl, dev_data=dev_dl, test_data=test_dl, model=model, args=args, logger=logger,
                          writer=None)
     trainer.train(clip_sd, bert_sd)  # None, None without --pretrained: randomly initialised encoders
     if trainer.samples_per_sec:
         logger.info("training throughput: %.1f samples/s on %d GPU(s)", trainer.samples_per_sec, world)
+    if args.write_path is not None:  # with the weights test() ran on: the best checkpoint when the run saved one
+        trainer.predict(test_dl, args.write_path)
 
 
 if __name__ == "__main__":

@@ -12,6 +12,7 @@ state-dict key names (:210-216).  Differences, all deliberate (SURVEY.md Appendi
 """
 from __future__ import annotations
 
+import json
 import logging
 import os
 import shutil
@@ -32,6 +33,17 @@ def get_four_metrics(labels, predicted_labels, type="weighted"):
     from sklearn.metrics import accuracy_score, precision_recall_fscore_support
     precision, recall, f1, _ = precision_recall_fscore_support(labels, predicted_labels, average=type, zero_division="warn")
     return accuracy_score(labels, predicted_labels), recall, precision, f1
+
+
+def write_predictions(path, ids, labels, preds, probs, paths_text, paths_image):
+    """JSON Lines, one object per sample in dataset order: {"index", "id", "label", "pred", "probs", "paths_text", "paths_image"}.
+    ids / labels: host lists (None where unknown); preds: int64 [N]; probs, paths_*: fp32 [N, *] host tensors.  Every float is the
+    fp32 value as a Python float, so it reads back exactly."""
+    preds, probs, pt, pi = preds.tolist(), probs.tolist(), paths_text.tolist(), paths_image.tolist()
+    with open(path, "w", encoding="utf-8") as f:
+        for i in range(len(preds)):
+            f.write(json.dumps({"index": i, "id": ids[i], "label": labels[i], "pred": preds[i], "probs": probs[i],
+                                "paths_text": pt[i], "paths_image": pi[i]}) + "\n")
 
 
 def _pretrained_source(name: str):
@@ -250,6 +262,61 @@ class MSDTrainer:
             self.writer.add_scalar(tag="test_loss", scalar_value=result["loss"] / len(self.test_data))
         self.model.train()
         return result
+
+    def predict(self, data, write_path=None):
+        """Label-free prediction over `data` (eval mode, no_grad): logits, class probabilities (d2r_softmax_fwd), predicted class
+        (d2r_argmax_rows) and the per-sample router outputs of both routing modules stay on the device across batches and are
+        copied to the host once at the end.  Metrics (test()'s four) when every sample is labelled (label >= 0); JSON Lines
+        records (write_predictions) with `write_path`.  -> dict of host tensors / lists, "metrics" (or None), "samples_per_sec"."""
+        self.model.eval()
+        self.logger.info("***** Running prediction *****")
+        self.logger.info("  Num instance = %d", len(data.dataset))
+        self.logger.info("  Batch size = %d", data.batch_size)
+        ds = data.dataset
+        in_order = isinstance(data.sampler, torch.utils.data.SequentialSampler)
+        logits_l, probs_l, preds_l, pt_l, pi_l, labels_l = [], [], [], [], [], []
+        t0 = time.time()
+        with torch.no_grad():
+            for packed in data:
+                input_ids, input_mask, segment_ids, _, _, images = self._to_device(packed)
+                self.decode_log.note(packed)  # after _to_device: a device-decoded batch has its status tensor from then on
+                _, logits = self.model(input_ids=input_ids, attention_mask=input_mask, token_type_ids=segment_ids, labels=None,
+                                       images=images)
+                aux = self.model.last_aux
+                logits_l.append(logits)
+                probs_l.append(F.softmax_rows(logits))
+                preds_l.append(F.argmax_rows(logits))
+                pt_l.append(aux["paths_text"])
+                pi_l.append(aux["paths_image"])
+                labels_l.append(packed[4])  # the loader's host copy: no device round trip
+        if not logits_l:
+            raise ValueError("predict: the loader yielded no batch")
+        dev = [torch.cat(x) for x in (logits_l, probs_l, preds_l, pt_l, pi_l)]
+        logits, probs, preds, paths_text, paths_image = [t.cpu() for t in dev]  # the one copy to the host
+        n = int(preds.shape[0])
+        self.samples_per_sec = n / max(time.time() - t0, 1e-9)
+        self.decode_log.end_pass("prediction")
+        labels = [int(y) if y >= 0 else None for y in torch.cat(labels_l).view(-1).tolist()]  # -1: unlabelled
+        ids = [ds.ids[i] for i in range(n)] if in_order and hasattr(ds, "ids") else [None] * n
+        metrics = None
+        if n and all(y is not None for y in labels):
+            acc, recall, precision, f1 = get_four_metrics(labels, preds.tolist(), type="weighted")
+            metrics = {"eval_accuracy": acc, "precision": precision, "recall": recall, "f_score": f1}
+            self.logger.info("***** Prediction results *****")
+            for key in sorted(metrics.keys()):
+                self.logger.info("  %s = %s", key, str(metrics[key]))
+        else:
+            self.logger.info("***** Prediction results *****: not every sample is labelled, no metrics computed")
+        self.logger.info("prediction throughput: %.1f samples/s (%d samples)", self.samples_per_sec, n)
+        if write_path is not None:
+            d = os.path.dirname(write_path)
+            if d:
+                os.makedirs(d, exist_ok=True)
+            write_predictions(write_path, ids, labels, preds, probs, paths_text, paths_image)
+            self.logger.info("Wrote %d predictions to %s", n, write_path)
+        self.model.train()
+        return {"ids": ids, "labels": labels, "logits": logits, "probs": probs, "preds": preds, "paths_text": paths_text,
+                "paths_image": paths_image, "metrics": metrics, "samples_per_sec": self.samples_per_sec}
 
     def _step(self, batch, mode="train"):
         input_ids, input_mask, segment_ids, img_mask, labels, images = batch  # img_mask is unused (train.py:281-284)

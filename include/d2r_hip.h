@@ -288,6 +288,10 @@ int d2r_jsdiv_bwd(const float* p_logits, const float* q_logits, int B, const flo
 int d2r_ce_fwd(const float* logits, const int64_t* labels, int B, int C, float* loss /*[1]*/, void* stream);
 int d2r_ce_bwd(const float* logits, const int64_t* labels, int B, int C, const float* dloss /*[1]*/,
                float* dlogits, void* stream);
+/* Predicted class per row of fp32 X[rows, cols] (row stride ld >= cols): idx[r] = argmax_c X[r, c], with torch.argmax's rules -
+ * a tie goes to the lowest index, a NaN counts as the maximum and the first NaN of a row wins, +-inf compare as usual.
+ * Replaces logits.argmax(-1) at modules/train.py:181,243 (prediction from a checkpoint).  rows == 0 launches nothing. */
+int d2r_argmax_rows(const float* X, int64_t ld, int64_t rows, int cols, int64_t* idx /*[rows]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K10 Block fusion core (models/XModules.py:541-549): z[b,c,s] = sum_r m0[b,c,r,s]*m1[b,c,r,s];
@@ -523,8 +527,8 @@ typedef struct {
   int B, E, mm, chunks, rank, classes;
   d2r_linear_params lin0, lin1, merge0, merge1, lin_out, fc;   /* fp32 weights */
   const float* x0; const float* x1;     /* fp32 [B, E]: pooled text / image vectors (Block's two inputs) */
-  const int64_t* labels;                /* [B] */
-  const float* js;                      /* fp32 [1]: the JS term of the loss */
+  const int64_t* labels;                /* [B]; NULL in the forward call: logits / pooled only (below) */
+  const float* js;                      /* fp32 [1]: the JS term of the loss (may be NULL when labels is) */
   float* loss; float* logits; float* pooled;   /* [1], [B, classes], [B, E] (Block's output)  OVERWRITTEN */
   void* arena; size_t arena_bytes;      /* forward activations kept for the backward call: >= d2r_head_arena_bytes() */
   void* splitk_ws; size_t splitk_bytes; /* split-K scratch of the weight-gradient GEMMs (may be NULL) */
@@ -538,6 +542,9 @@ typedef struct {
 } d2r_head_desc;
 size_t d2r_head_arena_bytes(int B, int E, int mm, int chunks, int rank, int classes);
 size_t d2r_head_bwd_scratch(int B, int E, int mm, int chunks, int rank, int classes);
+/* Prediction without labels: d2r_head_fwd with labels == NULL runs Block fusion, linear_out and fc as with labels and writes pooled
+ * and logits only (no cross entropy, no sum; loss and js may then be NULL).  d2r_head_bwd always needs labels (there is no loss to
+ * differentiate without them). */
 int d2r_head_fwd(const d2r_head_desc* d, void* stream);
 int d2r_head_bwd(const d2r_head_desc* d, void* stream);
 
