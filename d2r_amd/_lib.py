@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libd2r_hip.so")
 F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_GELU, ACT_QUICK_GELU, ACT_TANH_RELU, ACT_SIGMOID = range(7)
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
+GRAD_NORM_PARTS, GRAD_NORM_MAX_RANGES = 2048, 16  # D2R_GRAD_NORM_PARTS / D2R_GRAD_NORM_MAX_RANGES of include/d2r_hip.h
 
 vp, i32, i64, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
@@ -194,6 +195,10 @@ SIGNATURES = {
     "d2r_adamw_step": (i32, [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, i64, f32, vp, vp]),
     "d2r_adamw_step_dev": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, f32, f32, f32, f32, vp, vp]),
     "d2r_grad_nonfinite": (i32, [vp, i64, vp, vp]),
+    "d2r_adamw_step_clip": (i32, [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, i64, f32, vp, vp, vp]),
+    "d2r_adamw_step_dev_clip": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, f32, f32, f32, f32, vp, vp, vp]),
+    "d2r_grad_sumsq": (i32, [vp, vp, i32, vp, i64, vp]),
+    "d2r_grad_norm_finish": (i32, [vp, i64, f32, vp, f32, vp, vp, vp]),
     "d2r_copy_rows": (i32, [vp, i64, vp, i64, i64, i64, vp]),
 }
 

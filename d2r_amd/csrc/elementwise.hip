@@ -351,12 +351,15 @@ __device__ __forceinline__ void st4(float* p, const Pack<float, 4>& v) {
   }
 }
 
-template <typename H, bool NT>
+// CLIP: the gradient is also multiplied by the clipping coefficient *d_coef (d2r_grad_norm_finish), AFTER the unscale, as
+// clip_grad_norm_ multiplies the already unscaled gradient: (g * gscale) * coef, two roundings.  CLIP = false is the plain step.
+template <typename H, bool NT, bool CLIP>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ w, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     H* __restrict__ w16, int64_t n, float lr, float b1, float b2,
                                                     float eps, float wd, float bc1, float bc2_sqrt, float gscale,
-                                                    const float* __restrict__ d_hyper, const int* __restrict__ d_skip) {
+                                                    const float* __restrict__ d_hyper, const int* __restrict__ d_skip,
+                                                    const float* __restrict__ d_coef) {
   if (d_skip && *d_skip) return;  // overflowed loss-scaled gradients: this step is dropped
   if (d_hyper) {  // hipGraph-safe variant: per-step scalars live in device memory, refreshed before each replay
     lr = d_hyper[0];
@@ -364,11 +367,14 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ w, const
     bc2_sqrt = d_hyper[2];
     gscale = d_hyper[3];
   }
+  float coef = 1.f;
+  if constexpr (CLIP) coef = *d_coef;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
   const int64_t n4 = n / 4;
   auto upd = [&](float& wi, float gi, float& mi, float& vi) {
     gi *= gscale;
+    if constexpr (CLIP) gi *= coef;
     wi *= (1.f - lr * wd);                       // decoupled weight decay
     mi = b1 * mi + (1.f - b1) * gi;
     vi = b2 * vi + (1.f - b2) * gi * gi;
@@ -403,7 +409,7 @@ extern "C" void d2r_adamw_probe_mode(int nt, int blocks) { g_adamw_nt = nt, g_ad
 
 static int adamw_launch(const char* name, float* w, const float* g, float* m, float* v, void* w16, int w16_dtype, int64_t n, float lr,
                         float b1, float b2, float eps, float wd, float bc1, float bc2s, float gscale, const float* d_hyper,
-                        const int* d_skip, void* stream) {
+                        const int* d_skip, const float* d_coef, void* stream) {
   D2R_REQUIRE(d2r_aligned16(w) && d2r_aligned16(g) && d2r_aligned16(m) && d2r_aligned16(v), "%s: pointers must be 16-byte aligned", name);
   D2R_REQUIRE(!w16 || ((reinterpret_cast<uintptr_t>(w16) & 7u) == 0 && d2r_is16(w16_dtype)),
               "%s: the 16-bit shadow must be 8-byte aligned and D2R_BF16 or D2R_F16 (got dtype %d)", name, w16_dtype);
@@ -411,16 +417,20 @@ static int adamw_launch(const char* name, float* w, const float* g, float* m, fl
   int blocks = (int)((n / 4 + 256) / 256);
   const int cap = g_adamw_blocks > 0 ? g_adamw_blocks : 2048;
   if (blocks > cap) blocks = cap;
-#define D2R_ADAMW_LAUNCH(H, NT) \
-  hipLaunchKernelGGL((adamw_kernel<H, NT>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, g, m, v, (H*)w16, n, lr, b1, b2, eps, wd, bc1, bc2s, \
-                     gscale, d_hyper, d_skip)
+#define D2R_ADAMW_LAUNCH(H, NT, CLIP) \
+  hipLaunchKernelGGL((adamw_kernel<H, NT, CLIP>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, g, m, v, (H*)w16, n, lr, b1, b2, eps, wd, \
+                     bc1, bc2s, gscale, d_hyper, d_skip, d_coef)
+#define D2R_ADAMW_LAUNCH_NT(H, CLIP)       \
+  if (g_adamw_nt) D2R_ADAMW_LAUNCH(H, true, CLIP); \
+  else D2R_ADAMW_LAUNCH(H, false, CLIP)
   if (w16 && w16_dtype == D2R_F16) {
-    if (g_adamw_nt) D2R_ADAMW_LAUNCH(f16_t, true);
-    else D2R_ADAMW_LAUNCH(f16_t, false);
+    if (d_coef) { D2R_ADAMW_LAUNCH_NT(f16_t, true); }
+    else { D2R_ADAMW_LAUNCH_NT(f16_t, false); }
   } else {
-    if (g_adamw_nt) D2R_ADAMW_LAUNCH(bf16_t, true);
-    else D2R_ADAMW_LAUNCH(bf16_t, false);
+    if (d_coef) { D2R_ADAMW_LAUNCH_NT(bf16_t, true); }
+    else { D2R_ADAMW_LAUNCH_NT(bf16_t, false); }
   }
+#undef D2R_ADAMW_LAUNCH_NT
 #undef D2R_ADAMW_LAUNCH
   return d2r_check_launch(name);
 }
@@ -433,7 +443,18 @@ extern "C" int d2r_adamw_step(float* w, const float* g, float* m, float* v, void
   const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
   const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   return adamw_launch("d2r_adamw_step", w, g, m, v, w16, w16_dtype, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale,
-                      nullptr, d_skip, stream);
+                      nullptr, d_skip, nullptr, stream);
+}
+
+// the eager step with gradient clipping: d_coef = the coefficient d2r_grad_norm_finish wrote (device float)
+extern "C" int d2r_adamw_step_clip(float* w, const float* g, float* m, float* v, void* w16, int w16_dtype, int64_t n, float lr,
+                                   float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                                   const int* d_skip, const float* d_coef, void* stream) {
+  D2R_REQUIRE(w && g && m && v && d_coef && n >= 0 && step >= 1, "d2r_adamw_step_clip: bad arguments");
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  return adamw_launch("d2r_adamw_step_clip", w, g, m, v, w16, w16_dtype, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale,
+                      nullptr, d_skip, d_coef, stream);
 }
 
 // hipGraph-capturable form: d_hyper = device float[4] {lr, 1-beta1^t, sqrt(1-beta2^t), grad_scale}
@@ -442,7 +463,14 @@ extern "C" int d2r_adamw_step_dev(float* w, const float* g, float* m, float* v, 
                                   const int* d_skip, void* stream) {
   D2R_REQUIRE(w && g && m && v && d_hyper && n >= 0, "d2r_adamw_step_dev: bad arguments");
   return adamw_launch("d2r_adamw_step_dev", w, g, m, v, w16, w16_dtype, n, 0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, 1.f, d_hyper,
-                      d_skip, stream);
+                      d_skip, nullptr, stream);
+}
+extern "C" int d2r_adamw_step_dev_clip(float* w, const float* g, float* m, float* v, void* w16, int w16_dtype, int64_t n,
+                                       const float* d_hyper, float beta1, float beta2, float eps, float weight_decay,
+                                       const int* d_skip, const float* d_coef, void* stream) {
+  D2R_REQUIRE(w && g && m && v && d_hyper && d_coef && n >= 0, "d2r_adamw_step_dev_clip: bad arguments");
+  return adamw_launch("d2r_adamw_step_dev_clip", w, g, m, v, w16, w16_dtype, n, 0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, 1.f,
+                      d_hyper, d_skip, d_coef, stream);
 }
 
 // ---- overflow check of loss-scaled gradients (fp16 compute dtype): one streaming pass, flag |= any(!isfinite(g)) -----
@@ -466,4 +494,112 @@ extern "C" int d2r_grad_nonfinite(const float* g, int64_t n, int* d_flag, void* 
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(nonfinite_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n, d_flag);
   return d2r_check_launch("d2r_grad_nonfinite");
+}
+
+// ---- global L2 norm of the gradient for clipping (torch.nn.utils.clip_grad_norm_, norm type 2; an extension beyond the reference) --
+// Pass 1, d2r_grad_sumsq: a fixed grid of D2R_GRAD_NORM_PARTS workgroups; every thread adds the squares of its grid-stride share of
+// each range in fp64 (the square of an fp32 value is exact there and 3.5e8 squares of |g| <= 3.4e38 stay far below the fp64
+// limit, so loss-scaled gradients cannot overflow the sum), and every workgroup stores ONE fp64 partial - no atomics, so the same
+// gradients give the same bits on every run.  A partial is finite exactly when every gradient it covers is.
+// Pass 2, d2r_grad_norm_finish: one workgroup sums the partials in a fixed order and writes {norm, coef}.
+struct GradRanges {
+  int64_t lo[D2R_GRAD_NORM_MAX_RANGES], hi[D2R_GRAD_NORM_MAX_RANGES];
+  int n;
+};
+
+__device__ __forceinline__ void sumsq4(double& acc, const Pack<float, 4>& p) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const double x = (double)p.v[j];
+    acc = fma(x, x, acc);
+  }
+}
+
+// fixed-order sum over a 256-thread workgroup (the xor butterfly leaves the same bits in every lane); every thread gets the sum
+__device__ __forceinline__ double block_sum_f64_256(double v, double* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, GradRanges r, double* __restrict__ part) {
+  __shared__ double sh[4];
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  double acc = 0.0;
+  for (int i = 0; i < r.n; ++i) {
+    const float* p = g + r.lo[i];
+    const int64_t n = r.hi[i] - r.lo[i], n4 = n / 4;
+    int64_t k = tid;
+    for (; k + 3 * nthreads < n4; k += 4 * nthreads) {  // four 16-byte loads in flight, added in index order
+      const Pack<float, 4> a = ld_pack<float, 4>(p + k * 4), b = ld_pack<float, 4>(p + (k + nthreads) * 4);
+      const Pack<float, 4> c = ld_pack<float, 4>(p + (k + 2 * nthreads) * 4), d = ld_pack<float, 4>(p + (k + 3 * nthreads) * 4);
+      sumsq4(acc, a);
+      sumsq4(acc, b);
+      sumsq4(acc, c);
+      sumsq4(acc, d);
+    }
+    for (; k < n4; k += nthreads) sumsq4(acc, ld_pack<float, 4>(p + k * 4));
+    for (int64_t e = n4 * 4 + tid; e < n; e += nthreads) {
+      const double x = (double)p[e];
+      acc = fma(x, x, acc);
+    }
+  }
+  acc = block_sum_f64_256(acc, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+extern "C" int d2r_grad_sumsq(const float* g, const int64_t* h_ranges, int nranges, double* slab, int64_t slab_len, void* stream) {
+  D2R_REQUIRE(slab && (h_ranges || nranges == 0), "d2r_grad_sumsq: null pointer");
+  D2R_REQUIRE(nranges >= 0 && nranges <= D2R_GRAD_NORM_MAX_RANGES, "d2r_grad_sumsq: %d ranges (at most %d per call)", nranges,
+              D2R_GRAD_NORM_MAX_RANGES);
+  D2R_REQUIRE(slab_len >= D2R_GRAD_NORM_PARTS, "d2r_grad_sumsq: the slab holds %lld partials, a call writes %d", (long long)slab_len,
+              D2R_GRAD_NORM_PARTS);
+  GradRanges r;
+  memset(&r, 0, sizeof(r));
+  r.n = nranges;
+  bool empty = true;
+  for (int i = 0; i < nranges; ++i) {
+    const int64_t lo = h_ranges[2 * i], hi = h_ranges[2 * i + 1];
+    D2R_REQUIRE(lo >= 0 && hi >= lo, "d2r_grad_sumsq: range %d = [%lld, %lld) is not a range", i, (long long)lo, (long long)hi);
+    D2R_REQUIRE(lo % 4 == 0, "d2r_grad_sumsq: range %d starts at element %lld, not on a 16-byte boundary", i, (long long)lo);
+    r.lo[i] = lo, r.hi[i] = hi;
+    empty &= hi == lo;
+  }
+  // (an empty buffer may have no address: g is only needed when there is something to read)
+  D2R_REQUIRE(empty || (g && d2r_aligned16(g)), "d2r_grad_sumsq: the gradient must be a 16-byte aligned device pointer");
+  // always the full grid, empty ranges included: every partial of the slab is written (zeros where there is nothing to add)
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(D2R_GRAD_NORM_PARTS), dim3(256), 0, (hipStream_t)stream, g, r, slab);
+  return d2r_check_launch("d2r_grad_sumsq");
+}
+
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ part, int64_t nparts, float unscale,
+                                                               const float* __restrict__ d_unscale, float max_norm, float* __restrict__ out,
+                                                               int* __restrict__ flag) {
+  __shared__ double sh[4];
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < nparts; i += 256) acc += part[i];
+  const double total = block_sum_f64_256(acc, sh);
+  if (threadIdx.x == 0) {
+    const double us = (double)(d_unscale ? *d_unscale : unscale);
+    const float norm = (float)(sqrt(total) * us);  // one rounding; with a power-of-two unscale the same bits as the unscaled sum's norm
+    // torch: clamp(max_norm / (total_norm + 1e-6), max=1) in fp32, where `scalar / tensor` is reciprocal(tensor) * scalar;
+    // clamp keeps a NaN
+    const float q = (1.f / (norm + 1e-6f)) * max_norm;
+    out[0] = norm;
+    out[1] = (q < 1.f || q != q) ? q : 1.f;
+    if (flag && !(total <= 1.7976931348623157e308)) *flag = 1;  // an inf or a NaN among the gradients: a dropped loss-scaled step
+  }
+}
+
+extern "C" int d2r_grad_norm_finish(const double* slab, int64_t nparts, float unscale, const float* d_unscale, float max_norm, float* d_out,
+                                    int* d_flag, void* stream) {
+  D2R_REQUIRE(slab && d_out, "d2r_grad_norm_finish: null pointer");
+  D2R_REQUIRE(nparts >= 1, "d2r_grad_norm_finish: no partials");
+  D2R_REQUIRE(max_norm > 0.f, "d2r_grad_norm_finish: max_norm must be positive (got %g)", (double)max_norm);
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, slab, nparts, unscale, d_unscale, max_norm, d_out,
+                     d_flag);
+  return d2r_check_launch("d2r_grad_norm_finish");
 }

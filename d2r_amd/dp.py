@@ -77,6 +77,24 @@ def stripe_bounds(a: int, b: int, rank: int, world: int):
     return (a + rank * per, a + (rank + 1) * per), (a, a + per * world), (a + per * world, b)
 
 
+def bucket_bounds(n: int, bucket_elems: int, world: int, striped: bool):
+    """Buckets [a, b) of a flat buffer of n elements.  Striped modes (reduce-scatter): bucket lengths a multiple of 4 * world,
+    so that only the last bucket can have a tail."""
+    if striped:
+        q = 4 * world
+        bucket_elems = max(q, bucket_elems // q * q)
+    return [(a, min(n, a + bucket_elems)) for a in range(0, n, bucket_elems)]
+
+
+def norm_element_ranges(stripes, rank: int):
+    """Sharded optimiser, gradient clipping: the element ranges whose squared gradients rank `rank` adds into the global norm -
+    its own stripe of every bucket, and the bucket tails (which every rank owns and updates) on rank 0 only, so that no
+    element is counted twice.  `stripes`: the rank's stripe_bounds of every bucket."""
+    own = [o for o, _, _ in stripes if o[1] > o[0]]
+    tails = [t for _, _, t in stripes if t[1] > t[0]] if rank == 0 else []
+    return sorted(own + tails)
+
+
 class FlatGradReducer:
     """Bucketed SUM reduction of a flat fp32 gradient buffer.
 
@@ -96,11 +114,8 @@ class FlatGradReducer:
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         assert mode in ("all_reduce", "reduce_scatter_all_gather", "reduce_scatter"), mode
         self.mode = mode
-        n = flat_g.numel()
-        if mode != "all_reduce":  # stripes of 4 * k elements: keep the buckets a multiple of 4 * world so that only the last has a tail
-            q = 4 * self.world
-            bucket_elems = max(q, bucket_elems // q * q)
-        self.bounds = [(a, min(n, a + bucket_elems)) for a in range(0, n, bucket_elems)]
+        # stripes of 4 * k elements: keep the buckets a multiple of 4 * world so that only the last has a tail
+        self.bounds = bucket_bounds(flat_g.numel(), bucket_elems, self.world, mode != "all_reduce")
         self.stripes = [stripe_bounds(a, b, self.rank, self.world) for a, b in self.bounds]
         self.handles = []
         self.comm_stream = torch.cuda.Stream() if flat_g.is_cuda else None
@@ -235,6 +250,7 @@ class DataParallel:
             # this rank updates its stripe of every bucket, and every rank updates the (tiny) bucket tails
             optimizer.element_ranges = [r for own, _, tail in self.reducer.stripes for r in (own, tail) if r[1] > r[0]]
             optimizer.shard_gather = self.reducer.gather_stripes
+            optimizer.norm_element_ranges = norm_element_ranges(self.reducer.stripes, self.rank)
         self.overlap = overlap and self.active
         self._pending: List[int] = []
         self._bucket_of = {}

@@ -185,12 +185,38 @@ class ParamStore:
         return sum(k for _, _, _, k, _ in self.entries)
 
 
+def intersect_ranges(ranges, limits=None):
+    """The parts of the element ranges `ranges` that lie inside `limits` (None: no limit), sorted, adjacent parts merged."""
+    parts = []
+    for a, b in ranges:
+        for lo, hi in ([(a, b)] if limits is None else limits):
+            x, y = max(a, lo), min(b, hi)
+            if y > x:
+                parts.append((x, y))
+    out = []
+    for x, y in sorted(parts):
+        if out and x <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], y))
+        else:
+            out.append((x, y))
+    return out
+
+
 class FusedAdamW:
     """torch.optim.AdamW semantics (betas 0.9/0.999, eps 1e-8, decoupled weight decay) as one HIP launch per
-    parameter group over the flat buffers (K14)."""
+    parameter group over the flat buffers (K14).
+
+    max_grad_norm = c > 0 clips the gradient by its global L2 norm first, as ``torch.nn.utils.clip_grad_norm_(params, c)``
+    before ``step()`` would (an extension beyond the reference): a streaming fp64 sum of squares over the ranges this rank
+    updates (d2r_grad_sumsq), one launch that turns it into {norm, coef} on the device (d2r_grad_norm_finish), and AdamW
+    reading coef.  The pre-clip norm stays on the device (``last_grad_norm``, fp32 scalar).  None or 0: off."""
 
     def __init__(self, store: ParamStore, lr: float, fc_lr: float = 5e-2, weight_decay: float = 1e-2,
-                 betas=(0.9, 0.999), eps: float = 1e-8):
+                 betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = None):
+        if max_grad_norm is not None and not max_grad_norm >= 0:
+            raise ValueError(f"max_grad_norm must be None or >= 0, got {max_grad_norm}")
+        self.max_grad_norm = float(max_grad_norm) if max_grad_norm else None
+        self.last_grad_norm = None
         self.store = store
         self.betas, self.eps = betas, eps
         self.m = torch.zeros_like(store.flat_w)
@@ -204,6 +230,8 @@ class FusedAdamW:
         self.element_ranges = None
         self.shard_gather = None
         self.dp_group = None
+        # ... and, of those, the ranges whose gradients it adds into the global norm (the bucket tails on one rank only)
+        self.norm_element_ranges = None
         names = {0: "other", 1: "text", 2: "vision", 3: "fc"}
         self.param_groups = []
         for g, (a, b) in sorted(store.group_ranges.items()):
@@ -212,6 +240,8 @@ class FusedAdamW:
                                           weight_decay=weight_decay))
         if store.flat_w.is_cuda:  # created eagerly, not inside a stream capture
             self._hyper_buffers()
+            if self.max_grad_norm is not None:
+                self._clip_buffers(1)
 
     def zero_grad(self, set_to_none: bool = False):
         self.store.zero_grad()
@@ -308,22 +338,84 @@ class FusedAdamW:
                 out.append((x, y))
         return out
 
+    # -- gradient clipping by global norm --------------------------------------------------------------
+    def _norm_ranges(self):
+        """The element ranges whose squared gradients this rank adds into the norm: every parameter group's range, or under the
+        sharded optimiser the part of them in norm_element_ranges (its stripes, plus the bucket tails on one rank)."""
+        limits = self.norm_element_ranges if self.element_ranges is not None else None
+        return intersect_ranges([pg["range"] for pg in self.param_groups], limits)
+
+    def _norm_world(self):
+        if self.element_ranges is None:
+            return 1
+        import torch.distributed as dist
+        return dist.get_world_size(self.dp_group) if dist.is_initialized() else 1
+
+    def _clip_buffers(self, world):
+        """{norm, coef} and the fp64 partials: this rank's (`slab`, one segment of GRAD_NORM_PARTS per d2r_grad_sumsq call) and, with
+        several ranks, every rank's side by side (`slab_all`).  Allocated outside any capture; the range list never changes, so a
+        segment nothing is written to stays zero."""
+        nseg = max(1, -(-(len(self.param_groups) + len(self.element_ranges or ())) // _lib.GRAD_NORM_MAX_RANGES))
+        cb = getattr(self, "_clip", None)
+        if cb is None or cb["nseg"] != nseg or cb["world"] != world:
+            dev = self.store.flat_w.device
+            out = torch.zeros(2, dtype=torch.float32, device=dev)
+            slab = torch.zeros(nseg * _lib.GRAD_NORM_PARTS, dtype=torch.float64, device=dev)
+            cb = self._clip = dict(nseg=nseg, world=world, out=out, slab=slab,
+                                   slab_all=slab if world == 1 else torch.zeros(world * slab.numel(), dtype=torch.float64, device=dev))
+            self.last_grad_norm = out[0]
+        return cb
+
+    def _clip_coef(self, unscale: float, d_unscale, flag):
+        """Norm pass + finish; -> device address of coef.  `flag` (loss scaling): raised when a gradient is an inf or a NaN."""
+        import ctypes as C
+        world = self._norm_world()
+        cb = self._clip_buffers(world)
+        ranges = self._norm_ranges()
+        per = _lib.GRAD_NORM_MAX_RANGES
+        chunks = [ranges[i:i + per] for i in range(0, len(ranges), per)] or [[]]
+        assert len(chunks) <= cb["nseg"], (len(ranges), cb["nseg"])
+        g = self.store.flat_g.data_ptr()
+        for j, ch in enumerate(chunks):
+            arr = (C.c_int64 * max(1, 2 * len(ch)))(*[x for r in ch for x in r])
+            _lib.call("d2r_grad_sumsq", g, arr, len(ch), cb["slab"].data_ptr() + 8 * j * _lib.GRAD_NORM_PARTS, _lib.GRAD_NORM_PARTS,
+                      _stream())
+        if world > 1:
+            # every rank gets every rank's partials and sums them in the same fixed order: the same norm and coef, bit for bit, and
+            # (loss scaling) the same overflow flag - the one collective of the clipped step
+            import torch.distributed as dist
+            dist.all_gather_into_tensor(cb["slab_all"], cb["slab"], group=self.dp_group)
+        out = cb["out"]
+        _lib.call("d2r_grad_norm_finish", cb["slab_all"].data_ptr(), cb["slab_all"].numel(), unscale, d_unscale, self.max_grad_norm,
+                  out.data_ptr(), flag, _stream())
+        return out.data_ptr() + 4
+
     def step(self):
         from .functional import wgrad_join
         wgrad_join()
         used = self.loss_scale  # the scale this step's backward ran with (the host may change it below)
-        skip = None
+        skip = coef = None
         if self._scaler is not None:
-            self._scaler_before_step()
+            if self.max_grad_norm is None:
+                self._scaler_before_step()
+            else:  # the norm pass raises the overflow flag itself (no separate scan of the gradients)
+                self._scaler_consume()
+                self._scaler["flag"].zero_()
             skip = self._scaler["flag"].data_ptr()
+        if self.max_grad_norm is not None:
+            coef = self._clip_coef(self.grad_scale / used, None, skip)
         self.step_count += 1
         st = self.store
         for pg in self.param_groups:
             for a, b in self._owned(pg["range"]):
                 lp = None if st.flat_lp is None else st.flat_lp.data_ptr() + 2 * a
-                _lib.call("d2r_adamw_step", st.flat_w.data_ptr() + 4 * a, st.flat_g.data_ptr() + 4 * a,
-                          self.m.data_ptr() + 4 * a, self.v.data_ptr() + 4 * a, lp, st.lp_dtype, b - a, pg["lr"], self.betas[0],
-                          self.betas[1], self.eps, pg["weight_decay"], self.step_count, self.grad_scale / used, skip, _stream())
+                args = (st.flat_w.data_ptr() + 4 * a, st.flat_g.data_ptr() + 4 * a, self.m.data_ptr() + 4 * a, self.v.data_ptr() + 4 * a,
+                        lp, st.lp_dtype, b - a, pg["lr"], self.betas[0], self.betas[1], self.eps, pg["weight_decay"], self.step_count,
+                        self.grad_scale / used, skip)
+                if coef is None:
+                    _lib.call("d2r_adamw_step", *args, _stream())
+                else:
+                    _lib.call("d2r_adamw_step_clip", *args, coef, _stream())
         if self._scaler is not None:
             self._scaler_after_step()
 
@@ -367,20 +459,30 @@ class FusedAdamW:
         wgrad_join()
         st = self.store
         _, dev = self._hyper_buffers()
-        skip = None
+        skip = coef = None
+        if self.max_grad_norm is not None and self.element_ranges is not None:
+            raise RuntimeError("step_captured: the sharded optimiser's gradient norm needs a collective, which is not captured")
         if self._scaler is not None:
             if self.element_ranges is not None:
                 raise RuntimeError("step_captured: the sharded optimiser's overflow flag needs a collective, which is not captured")
-            self._scaler_arm()
+            if self.max_grad_norm is None:
+                self._scaler_arm()
+            else:
+                self._scaler["flag"].zero_()
             skip = self._scaler["flag"].data_ptr()
+        if self.max_grad_norm is not None:  # unscale factor from d_hyper (every group holds the same), max_norm baked in
+            coef = self._clip_coef(0.0, dev.data_ptr() + 12, skip)
         for i, pg in enumerate(self.param_groups):
             a, b = pg["range"]
             if b <= a:
                 continue
             lp = None if st.flat_lp is None else st.flat_lp.data_ptr() + 2 * a
-            _lib.call("d2r_adamw_step_dev", st.flat_w.data_ptr() + 4 * a, st.flat_g.data_ptr() + 4 * a,
-                      self.m.data_ptr() + 4 * a, self.v.data_ptr() + 4 * a, lp, st.lp_dtype, b - a, dev.data_ptr() + 16 * i,
-                      self.betas[0], self.betas[1], self.eps, pg["weight_decay"], skip, _stream())
+            args = (st.flat_w.data_ptr() + 4 * a, st.flat_g.data_ptr() + 4 * a, self.m.data_ptr() + 4 * a, self.v.data_ptr() + 4 * a,
+                    lp, st.lp_dtype, b - a, dev.data_ptr() + 16 * i, self.betas[0], self.betas[1], self.eps, pg["weight_decay"], skip)
+            if coef is None:
+                _lib.call("d2r_adamw_step_dev", *args, _stream())
+            else:
+                _lib.call("d2r_adamw_step_dev_clip", *args, coef, _stream())
 
     def after_replay(self):
         """Behind a replay of a captured step: starts the copy of the overflow flag (no-op without loss scaling)."""

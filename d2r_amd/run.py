@@ -34,6 +34,13 @@ def set_seed(seed=2023):
     random.seed(seed)
 
 
+def _max_grad_norm(text):
+    v = float(text)
+    if not v >= 0:
+        raise argparse.ArgumentTypeError(f"must be >= 0 (0 = no clipping), got {text}")
+    return v
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     # --- flags of the reference (run.py:39-84); unused ones are accepted and ignored like there
@@ -85,6 +92,8 @@ def build_parser():
     p.add_argument("--train_samples", default=512, type=int)
     p.add_argument("--eval_samples", default=128, type=int)
     p.add_argument("--num_workers", default=4, type=int)
+    p.add_argument("--max_grad_norm", default=0.0, type=_max_grad_norm, help="clip the gradient to this global L2 norm before every "
+                   "AdamW step, as torch.nn.utils.clip_grad_norm_ would (0 = off, the reference's behaviour)")
     p.add_argument("--dp_overlap", action="store_true")
     p.add_argument("--dp_grad_comm", default="f32", choices=["f32", "bf16"], help="dtype of the gradient buckets on the links")
     p.add_argument("--dp_shard_optimizer", action="store_true",

@@ -99,7 +99,8 @@ class MSDTrainer:
         self.store = ParamStore(self.model, dtype)
         from . import configure_runtime
         configure_runtime()
-        self.optimizer = FusedAdamW(self.store, lr=self.args.lr, fc_lr=5e-2, weight_decay=1e-2)
+        self.optimizer = FusedAdamW(self.store, lr=self.args.lr, fc_lr=5e-2, weight_decay=1e-2,
+                                    max_grad_norm=getattr(self.args, "max_grad_norm", None) or None)
         if dtype == torch.float16:  # fp16 activation gradients need a scaled loss (AMP's GradScaler, here inside the optimiser)
             self.optimizer.enable_loss_scaling()
         shard = bool(getattr(self.args, "dp_shard_optimizer", False))
@@ -141,6 +142,8 @@ class MSDTrainer:
             ingest_pretrained(self.model, clip_model_dict, bert_model_dict)
             self.store.refresh_lowp()
         run_loss = torch.zeros((), dtype=torch.float32, device=self.args.device)
+        clipping = self.optimizer.max_grad_norm is not None
+        grad_norm = torch.zeros((), dtype=torch.float32, pin_memory=torch.cuda.is_available()) if clipping else None
         # throughput of the TRAINING loop only: the clock starts after a few warm-up steps (first-touch allocations,
         # loader workers) and stops across evaluation
         t_train, t_mark, seen, warm = 0.0, None, 0, 5
@@ -169,12 +172,18 @@ class MSDTrainer:
                 if self.step > warm:
                     seen += int(labels.shape[0]) * self.dp.world
                 if self.step % self.refresh_step == 0:
+                    if clipping:  # the pre-clip norm of this step: lands with the sync below, no wait of its own
+                        grad_norm.copy_(self.optimizer.last_grad_norm, non_blocking=True)
                     avg_loss = float(run_loss.item()) / self.refresh_step  # the only host sync of the loop
                     run_loss.zero_()
                     self.decode_log.poll()  # decode status of the batches so far: complete after the sync above
                     if t_mark is not None and seen:
                         self.samples_per_sec = seen / max(t_train + time.time() - t_mark, 1e-9)
-                    self.logger.info("step %d loss:%-6.5f samples/s:%.1f", self.step, avg_loss, self.samples_per_sec or 0.0)
+                    if clipping:
+                        self.logger.info("step %d loss:%-6.5f samples/s:%.1f grad_norm:%.4f", self.step, avg_loss,
+                                         self.samples_per_sec or 0.0, float(grad_norm))
+                    else:
+                        self.logger.info("step %d loss:%-6.5f samples/s:%.1f", self.step, avg_loss, self.samples_per_sec or 0.0)
                     if self.writer:
                         self.writer.add_scalar(tag="train_loss", scalar_value=avg_loss, global_step=self.step)
             self.decode_log.end_epoch(epoch)

@@ -670,6 +670,29 @@ int d2r_adamw_step(float* w, const float* g, float* m, float* v, void* w16 /*or 
 int d2r_adamw_step_dev(float* w, const float* g, float* m, float* v, void* w16 /*or NULL*/, int w16_dtype, int64_t n,
                        const float* d_hyper, float beta1, float beta2, float eps, float weight_decay,
                        const int* d_skip /*or NULL*/, void* stream);
+/* Gradient clipping by global norm: torch.nn.utils.clip_grad_norm_(params, max_norm) (norm type 2, error_if_nonfinite=False)
+ * ahead of the AdamW step - an extension beyond the reference, which does not clip.
+ * The _clip forms of the two AdamW entry points above update with (g * grad_scale) * (*d_coef), d_coef = the coefficient
+ * d2r_grad_norm_finish wrote (device float); everything else as d2r_adamw_step / d2r_adamw_step_dev. */
+int d2r_adamw_step_clip(float* w, const float* g, float* m, float* v, void* w16 /*or NULL*/, int w16_dtype, int64_t n, float lr,
+                        float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                        const int* d_skip /*or NULL*/, const float* d_coef, void* stream);
+int d2r_adamw_step_dev_clip(float* w, const float* g, float* m, float* v, void* w16 /*or NULL*/, int w16_dtype, int64_t n,
+                            const float* d_hyper, float beta1, float beta2, float eps, float weight_decay,
+                            const int* d_skip /*or NULL*/, const float* d_coef, void* stream);
+#define D2R_GRAD_NORM_PARTS 2048     /* fp64 partial sums one d2r_grad_sumsq call writes */
+#define D2R_GRAD_NORM_MAX_RANGES 16  /* element ranges one d2r_grad_sumsq call takes */
+/* slab[0..D2R_GRAD_NORM_PARTS) = fp64 partial sums of g[i]^2 over the element ranges h_ranges = host int64
+ * {lo0, hi0, lo1, hi1, ...} (nranges of them, each lo a multiple of 4; g 16-byte aligned).  Every partial is written on
+ * every call (zeros for empty ranges); the sum of the partials is the same bits on every run (no atomics). */
+int d2r_grad_sumsq(const float* g, const int64_t* h_ranges, int nranges, double* slab, int64_t slab_len, void* stream);
+/* total = fixed-order sum of slab[0..nparts) (the partials of one or more d2r_grad_sumsq calls, possibly gathered from
+ * several ranks); d_out[0] = norm = sqrt(total) * unscale (unscale = *d_unscale when d_unscale is not NULL: the hipGraph form
+ * reads d_hyper[3]), d_out[1] = coef = min(1, max_norm / (norm + 1e-6)) in fp32 as torch computes it (NaN stays NaN).
+ * d_flag (or NULL): set to 1 when total is not finite, i.e. some gradient is an inf or a NaN - the loss-scaled step's
+ * overflow flag, which this pass then raises instead of d2r_grad_nonfinite. */
+int d2r_grad_norm_finish(const double* slab, int64_t nparts, float unscale, const float* d_unscale /*or NULL*/, float max_norm,
+                         float* d_out, int* d_flag /*or NULL*/, void* stream);
 /* dst[r][0..width) = src[r][0..width) for r < rows; pitches and width in BYTES (16-byte vector path when everything is 16-byte
  * aligned).  One launch - the runtime's device-to-device hipMemcpy2DAsync issues one blit kernel per row for these shapes. */
 int d2r_copy_rows(void* dst, int64_t dst_pitch, const void* src, int64_t src_pitch, int64_t width, int64_t rows, void* stream);
