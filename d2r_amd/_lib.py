@@ -221,6 +221,9 @@ PROBE_SIGNATURES = {
     "d2r_xattn3_debug_stamps": (None, [vp]),
     "d2r_xattn3_debug_mode": (None, [i32]),
     "d2r_adamw_probe_mode": (None, [i32, i32]),
+    "d2r_attn_trace": (None, [i32]),
+    "d2r_attn_trace_read": (i32, [C.POINTER(i32), i32]),
+    "d2r_attn_trace_codes": (i32, [C.POINTER(i32), i32]),
 }
 
 

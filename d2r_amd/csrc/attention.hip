@@ -37,6 +37,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "attn_trace.h"
 #include "gemm_args.h"
 #include "ktimer.h"
 
@@ -60,6 +61,47 @@ int d2r_xattn3_dkv_try(int dtype, int ngroup, const void* const* W, const void* 
                        const int64_t* ldo, const int64_t* sob, const int* trans, int lkp, int B, int Lq, int Lk, hipStream_t st);
 int d2r_gemm_tn_batched16(int dtype, int M, int m_store, int N, int K, int64_t lda, int64_t sAb, int64_t ldb, int64_t sBb, int64_t ldc,
                           int64_t sCb, const void* const* A, const void* const* B, void* const* C, int ngroups, int nb, void* stream);  // gemm.hip
+
+// ---- record of the launched variants (attn_trace.h; d2r_attn_trace / _read / _codes of include/d2r_hip_probes.h) ----------------------
+bool g_d2r_attn_trace = false;
+namespace {
+constexpr int ATTN_TRACE_CAP = 4096;
+int g_attn_trace_n = 0;  // launches since arming (the list keeps the first ATTN_TRACE_CAP of them)
+int g_attn_trace_codes[ATTN_TRACE_CAP];
+}  // namespace
+void d2r_attn_trace_push(int code) {
+  if (g_attn_trace_n < ATTN_TRACE_CAP) g_attn_trace_codes[g_attn_trace_n] = code;
+  ++g_attn_trace_n;
+}
+extern "C" void d2r_attn_trace(int on) {
+  if (on) g_attn_trace_n = 0;
+  g_d2r_attn_trace = on != 0;
+}
+extern "C" int d2r_attn_trace_read(int* codes, int capacity) {
+  const int have = g_attn_trace_n < ATTN_TRACE_CAP ? g_attn_trace_n : ATTN_TRACE_CAP;
+  for (int i = 0; codes && i < have && i < capacity; ++i) codes[i] = g_attn_trace_codes[i];
+  return g_attn_trace_n;
+}
+extern "C" int d2r_attn_trace_codes(int* codes, int capacity) {
+  int n = 0;
+  auto put = [&](int code) {
+    if (codes && n < capacity) codes[n] = code;
+    ++n;
+  };
+  for (int dh : {64, 48}) {
+    for (int nk32 = 1; nk32 <= 8; ++nk32) put(D2R_AV_MHA_FWD + dh * 100 + nk32), put(D2R_AV_MHA_BWD + dh * 100 + nk32);
+    put(D2R_AV_MHA_LONG_FWD + dh * 100), put(D2R_AV_MHA_LONG_DQ + dh * 100), put(D2R_AV_MHA_LONG_DKV + dh * 100);
+  }
+  for (int code : {D2R_AV_X3_FWD, D2R_AV_X3_BWD, D2R_AV_X3_DKV, D2R_AV_X3_DKV2, D2R_AV_X2_FWD_2_256, D2R_AV_X2_FWD_1_256, D2R_AV_X2_FWD_1_640,
+                   D2R_AV_XBWD_2, D2R_AV_XBWD_5, D2R_AV_KEYSIDE_GROUPED, D2R_AV_KEYSIDE_DV, D2R_AV_KEYSIDE_DK})
+    put(code);
+  return n;
+}
+// a key-side product of the second generation: recorded when the GEMM entry point took it
+static int keyside(int code, int rc) {
+  if (rc == 0) d2r_attn_note(code);
+  return rc;
+}
 
 // one copy of the kernels per 16-bit element type
 namespace att_bf16 {
@@ -186,10 +228,14 @@ extern "C" int d2r_xattn_bwd_multi(int dtype, int ncore, const void* const* h_q,
       A[2 * c] = h_P[c], Bm[2 * c] = h_dO[c], C[2 * c] = h_dv[c];
       A[2 * c + 1] = h_dS[c], Bm[2 * c + 1] = h_q[c], C[2 * c + 1] = h_dk[c];
     }
-    return d2r_gemm_tn_batched16(dtype, lkp, Lk, D, Lq, lkp, (int64_t)Lq * lkp, ldq, sqb, lddk, sdkb, A, Bm, C, 2 * ncore, B, stream);
+    return keyside(D2R_AV_KEYSIDE_GROUPED,
+                   d2r_gemm_tn_batched16(dtype, lkp, Lk, D, Lq, lkp, (int64_t)Lq * lkp, ldq, sqb, lddk, sdkb, A, Bm, C, 2 * ncore, B, stream));
   }
   for (int c = 0; c < ncore; ++c) A[c] = h_P[c], Bm[c] = h_dO[c], C[c] = h_dv[c];
-  if (int rc = d2r_gemm_tn_batched16(dtype, lkp, Lk, D, Lq, lkp, (int64_t)Lq * lkp, ldg, sgb, lddv, sdvb, A, Bm, C, ncore, B, stream)) return rc;
+  if (int rc = keyside(D2R_AV_KEYSIDE_DV,
+                       d2r_gemm_tn_batched16(dtype, lkp, Lk, D, Lq, lkp, (int64_t)Lq * lkp, ldg, sgb, lddv, sdvb, A, Bm, C, ncore, B, stream)))
+    return rc;
   for (int c = 0; c < ncore; ++c) A[c] = h_dS[c], Bm[c] = h_q[c], C[c] = h_dk[c];
-  return d2r_gemm_tn_batched16(dtype, lkp, Lk, D, Lq, lkp, (int64_t)Lq * lkp, ldq, sqb, lddk, sdkb, A, Bm, C, ncore, B, stream);
+  return keyside(D2R_AV_KEYSIDE_DK,
+                 d2r_gemm_tn_batched16(dtype, lkp, Lk, D, Lq, lkp, (int64_t)Lq * lkp, ldq, sqb, lddk, sdkb, A, Bm, C, ncore, B, stream));
 }

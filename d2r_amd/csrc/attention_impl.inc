@@ -705,6 +705,7 @@ void launch_fwd(const MhaArgs& a, int nk32, hipStream_t st) {
     D2R_CASE(1) D2R_CASE(2) D2R_CASE(3) D2R_CASE(4) D2R_CASE(5) D2R_CASE(6) D2R_CASE(7) D2R_CASE(8)
 #undef D2R_CASE
   }
+  d2r_attn_note(D2R_AV_MHA_FWD + DH * 100 + nk32);
 }
 template <int DH>
 void launch_bwd(const MhaArgs& a, int nk32, hipStream_t st) {
@@ -714,6 +715,7 @@ void launch_bwd(const MhaArgs& a, int nk32, hipStream_t st) {
     D2R_CASE(1) D2R_CASE(2) D2R_CASE(3) D2R_CASE(4) D2R_CASE(5) D2R_CASE(6) D2R_CASE(7) D2R_CASE(8)
 #undef D2R_CASE
   }
+  d2r_attn_note(D2R_AV_MHA_BWD + DH * 100 + nk32);
 }
 
 }  // namespace
@@ -738,6 +740,7 @@ int mha_fwd_run(int dtype, const void* q, int64_t ldq, int64_t sqb, const void* 
     const dim3 grid(d2r_cdiv(Lq, LB), B * H);
     if (head_dim == 64) hipLaunchKernelGGL(mha_long_fwd_kernel<64>, grid, dim3(512), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(mha_long_fwd_kernel<48>, grid, dim3(512), 0, (hipStream_t)stream, a);
+    d2r_attn_note(D2R_AV_MHA_LONG_FWD + head_dim * 100);
     return d2r_check_launch("d2r_mha_fwd(long)");
   }
   const int nk32 = d2r_cdiv(Lk, 32);
@@ -777,6 +780,8 @@ int mha_bwd_run(int dtype, const void* q, int64_t ldq, int64_t sqb, const void* 
       hipLaunchKernelGGL(mha_long_bwd_dq_kernel<48>, gq, dim3(512), 0, (hipStream_t)stream, a);
       hipLaunchKernelGGL(mha_long_bwd_dkv_kernel<48>, gk, dim3(512), 0, (hipStream_t)stream, a);
     }
+    d2r_attn_note(D2R_AV_MHA_LONG_DQ + head_dim * 100);
+    d2r_attn_note(D2R_AV_MHA_LONG_DKV + head_dim * 100);
     return d2r_check_launch("d2r_mha_bwd(long)");
   }
   const int nk32 = d2r_cdiv(Lq > Lk ? Lq : Lk, 32);
@@ -786,16 +791,6 @@ int mha_bwd_run(int dtype, const void* q, int64_t ldq, int64_t sqb, const void* 
 }
 
 namespace {
-
-struct XattnArgs {
-  const E *q, *k, *v, *res, *dO;
-  E *o, *dq, *p_out, *ds_out;
-  const float* mask;
-  float* lse;
-  int64_t ldq, sqb, ldk, skb, ldv, svb, ldo, sob, ldr, srb, ldg, sgb, lddq, sdqb;
-  int B, Lq, Lk, lkp;
-  float scale;
-};
 
 constexpr int XB_MAXCORE = 4;  // attention problems ("cores") of one backward launch: same shapes and strides, own tensors
 struct XbwdArgs {
@@ -817,7 +812,6 @@ __device__ __forceinline__ P xb_pick(P const (&arr)[XB_MAXCORE], int core) {  //
 
 constexpr int XD = 768, XQ = 32, XW = 8, XCOLS = XD / XW;  // 96 output columns per wave
 constexpr int LDQ = XD + 8;                                  // Qs row stride (bf16)
-constexpr int LDP = 256 + 8;                                 // Ps row stride (bf16), keys padded to <= 256
 constexpr int LDV = XCOLS + 8;                               // V slab row stride (bf16)
 
 // S^T / dP^T style product for this wave's (up to NTI: tiles wave, wave + 8, ...) key tiles and both query tiles:
@@ -936,121 +930,6 @@ __device__ __forceinline__ void xattn_stage_rows(E* dst, const E* __restrict__ s
   for (int it = 0; it < 6; ++it) {
     const int c = tid + it * 512, row = c / (XD / 8), ch = c % (XD / 8);
     st_pack<E, 8>(dst + row * LDQ + ch * 8, v[it]);
-  }
-}
-
-__global__ __launch_bounds__(512) void xattn_fwd_kernel(XattnArgs a) {
-  // LDS: Qs [32][776] (phase 1) and the 8 private V slabs (phase 2) share one region; Ps, Ms, reductions beside it
-  constexpr int SLAB = 2 * 32 * LDV;  // bf16 elements per wave
-  constexpr int REGION = (XQ * LDQ > XW * SLAB) ? XQ * LDQ : XW * SLAB;
-  __shared__ __attribute__((aligned(16))) E region[REGION];
-  __shared__ __attribute__((aligned(16))) E Ps[XQ * LDP];
-  __shared__ __attribute__((aligned(16))) float Ms[256];
-  __shared__ float red[XW][XQ];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int b = blockIdx.y, q0 = blockIdx.x * XQ;
-  const int nk32 = (a.Lk + 31) / 32, nt16 = nk32 * 2;
-  E* Qs = region;
-  {  // stage the 32 query rows (clamped past Lq) and the key mask
-    xattn_stage_rows(Qs, a.q + b * a.sqb, a.ldq, q0, a.Lq, tid);
-    for (int key = tid; key < 256; key += 512)
-      Ms[key] = key < a.Lk ? (a.mask ? a.mask[(int64_t)b * a.Lk + key] : 0.f) : -INFINITY;
-  }
-  __syncthreads();
-  f32x4 s[2][2];
-  xattn_scores<2>(a.k + b * a.skb, a.ldk, a.Lk, Qs, wave, nt16, fr, fq, s);
-  // ---- softmax over keys for query columns (qt*16 + fr): in-lane, across the 4 lane groups, across the 8 waves --
-  float mx[2] = {-INFINITY, -INFINITY};
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti) {
-    const int t = wave + ti * XW;
-    if (t >= nt16) continue;
-    const f32x4 m4 = *reinterpret_cast<const f32x4*>(&Ms[t * 16 + fq * 4]);
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s[ti][qt][r] = s[ti][qt][r] * a.scale + m4[r];
-        mx[qt] = fmaxf(mx[qt], s[ti][qt][r]);
-      }
-  }
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    mx[qt] = group4_max(mx[qt]);
-    if (fq == 0) red[wave][qt * 16 + fr] = mx[qt];
-  }
-  __syncthreads();
-  float sum[2] = {0.f, 0.f};
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    float m = red[0][qt * 16 + fr];
-#pragma unroll
-    for (int w = 1; w < XW; ++w) m = fmaxf(m, red[w][qt * 16 + fr]);
-    mx[qt] = m;
-  }
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti) {
-    if (wave + ti * XW >= nt16) continue;
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s[ti][qt][r] = __expf(s[ti][qt][r] - mx[qt]);
-        sum[qt] += s[ti][qt][r];
-      }
-  }
-  __syncthreads();  // everyone has read the maxima: `red` is reused for the sums
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    sum[qt] = group4_sum(sum[qt]);
-    if (fq == 0) red[wave][qt * 16 + fr] = sum[qt];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    float t = red[0][qt * 16 + fr];
-#pragma unroll
-    for (int w = 1; w < XW; ++w) t += red[w][qt * 16 + fr];
-    sum[qt] = t;
-    if (wave == 0 && fq == 0 && q0 + qt * 16 + fr < a.Lq) a.lse[(int64_t)b * a.Lq + q0 + qt * 16 + fr] = mx[qt] + logf(t);
-  }
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti) {
-    const int t = wave + ti * XW;
-    if (t >= nt16) continue;
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-      const float inv = 1.f / sum[qt];
-      Pack<E, 4> pk;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) pk.v[r] = (E)(s[ti][qt][r] * inv);
-      st_pack<E, 4>(Ps + (qt * 16 + fr) * LDP + t * 16 + fq * 4, pk);
-    }
-  }
-  __syncthreads();  // Ps complete; Qs is dead: its region now holds the V slabs
-  f32x4 o[6][2];
-  xattn_apply<LDP>(a.v + b * a.svb, a.ldv, a.Lk, nk32, Ps, region + wave * SLAB, wave, lane, o);
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const int qrow = q0 + qt * 16 + fr;
-    if (qrow >= a.Lq) continue;
-    E* Og = a.o + b * a.sob + (int64_t)qrow * a.ldo + wave * XCOLS;
-    const E* Rg = a.res ? a.res + b * a.srb + (int64_t)qrow * a.ldr + wave * XCOLS : nullptr;
-#pragma unroll
-    for (int dt = 0; dt < 6; ++dt) {
-      const int c = dt * 16 + fq * 4;
-      Pack<E, 4> out;
-      if (Rg) {
-        const Pack<E, 4> rv = ld_pack<E, 4>(Rg + c);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) out.v[r] = (E)(o[dt][qt][r] + (float)rv.v[r]);
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) out.v[r] = (E)o[dt][qt][r];
-      }
-      st_pack<E, 4>(Og + c, out);
-    }
   }
 }
 
@@ -1177,16 +1056,8 @@ int xattn_fwd_run(int dtype, int ncore, const void* const* q, int64_t ldq, int64
   if (d2r_xattn2_fwd_try(dtype, ncore, q, ldq, sqb, k, ldk, skb, v, ldv, svb, o, ldo, sob, residual, ldr, srb, mask, lse, B, Lq, Lk,
                                    scale, (hipStream_t)stream))
     return d2r_check_launch("d2r_xattn_fwd(v2)");
-  D2R_REQUIRE(Lk <= 256, "d2r_xattn_fwd: the first-generation kernel holds at most 256 keys");
-  for (int c = 0; c < ncore; ++c) {  // first-generation kernel: one launch per problem
-    XattnArgs a = {};
-    a.q = (const E*)q[c], a.k = (const E*)k[c], a.v = (const E*)v[c], a.res = residual ? (const E*)residual[c] : nullptr, a.o = (E*)o[c];
-    a.mask = mask, a.lse = lse[c];
-    a.ldq = ldq, a.sqb = sqb, a.ldk = ldk, a.skb = skb, a.ldv = ldv, a.svb = svb, a.ldo = ldo, a.sob = sob, a.ldr = ldr, a.srb = srb;
-    a.B = B, a.Lq = Lq, a.Lk = Lk, a.scale = scale;
-    hipLaunchKernelGGL(xattn_fwd_kernel, dim3(d2r_cdiv(Lq, XQ), B), dim3(512), 0, (hipStream_t)stream, a);
-  }
-  return d2r_check_launch("d2r_xattn_fwd");
+  // (d2r_xattn2_fwd_try takes every shape the checks above let through: Lk <= 640, 1..4 problems)
+  return d2r_fail(D2R_ERR_INVALID, "d2r_xattn_fwd: no kernel for the shape");
 }
 
 // `ncore` (1..4) backward problems of identical shape and strides in one launch: dS, P (16-bit [B, Lq, lkp] each) and dQ.
@@ -1212,5 +1083,6 @@ int xattn_bwd_run(int dtype, int ncore, const void* const* q, int64_t ldq, int64
   const dim3 grid((B + 7) / 8 * 8 * a.ntile * ncore);
   if (Lk <= 256) hipLaunchKernelGGL(xattn_bwd_kernel<2>, grid, dim3(512), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(xattn_bwd_kernel<5>, grid, dim3(512), 0, (hipStream_t)stream, a);
+  d2r_attn_note(Lk <= 256 ? D2R_AV_XBWD_2 : D2R_AV_XBWD_5);
   return d2r_check_launch("d2r_xattn_bwd");
 }

@@ -22,6 +22,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "attn_trace.h"
 #include "gemm_args.h"
 
 // the ablation switches (D2R_X2_DBG) are compiled in only with -DD2R_X3_PROBES=1 (run-time branches in the tile loops otherwise)
@@ -299,13 +300,16 @@ static int x2_launch(int ncore, const void* const* q, int64_t ldq, int64_t sqb, 
     if (nt32 * B * ncore >= 192) {
       a.ntile = nt32;
       hipLaunchKernelGGL((xattn2_fwd_kernel<E, 2, 256>), dim3(bgrp * a.ntile * ncore), dim3(512), 0, st, a);
+      d2r_attn_note(D2R_AV_X2_FWD_2_256);
     } else {
       a.ntile = (Lq + 15) / 16;
       hipLaunchKernelGGL((xattn2_fwd_kernel<E, 1, 256>), dim3(bgrp * a.ntile * ncore), dim3(512), 0, st, a);
+      d2r_attn_note(D2R_AV_X2_FWD_1_256);
     }
   } else {
     a.ntile = (Lq + 15) / 16;
     hipLaunchKernelGGL((xattn2_fwd_kernel<E, 1, 640>), dim3(bgrp * a.ntile * ncore), dim3(512), 0, st, a);
+    d2r_attn_note(D2R_AV_X2_FWD_1_640);
   }
   return 1;
 }

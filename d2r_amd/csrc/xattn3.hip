@@ -33,6 +33,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "attn_trace.h"
 #include "gemm_args.h"
 
 #ifndef D2R_X3_PROBES
@@ -817,6 +818,7 @@ int x3_fwd_launch(int ncore, const void* const* q, int64_t ldq, int64_t sqb, con
   X3Args<E> a = {};
   x3_fill<E>(a, ncore, q, ldq, sqb, k, ldk, skb, v, ldv, svb, o, ldo, sob, residual, ldr, srb, mask, lse, B, Lq, Lk, scale);
   hipLaunchKernelGGL((xattn3_fwd_kernel<E, 256>), dim3((B + 7) / 8 * 8 * a.ntile * ncore), dim3(256), 0, st, a);
+  d2r_attn_note(D2R_AV_X3_FWD);
   return 1;
 }
 
@@ -831,6 +833,7 @@ int x3_bwd_launch(int ncore, const void* const* q, int64_t ldq, int64_t sqb, con
   for (int c = 0; c < ncore; ++c) a.dO[c] = (const E*)dO[c], a.p_out[c] = (E*)P[c], a.ds_out[c] = (E*)dS[c];
   a.lkp = lkp, a.ldg = ldg, a.sgb = sgb;
   hipLaunchKernelGGL((xattn3_bwd_kernel<E, 256>), dim3((B + 7) / 8 * 8 * a.ntile * ncore), dim3(256), 0, st, a);
+  d2r_attn_note(D2R_AV_X3_BWD);
   return 1;
 }
 
@@ -857,9 +860,11 @@ int x3_dkv_launch(int ngroup, const void* const* W, const void* const* X, void* 
   //  54 against 59 us for the three products of one 128 x 128 problem)
   if (compact && lds <= 65536 && (B + 7) / 8 * 8 * ngroup > 256) {
     hipLaunchKernelGGL((xattn3_dkv2_kernel<E>), dim3((B + 7) / 8 * 8 * ngroup), dim3(512), lds, st, a);
+    d2r_attn_note(D2R_AV_X3_DKV2);
     return 1;
   }
   hipLaunchKernelGGL((xattn3_dkv_kernel<E>), dim3((B + 7) / 8 * 8 * ngroup), dim3(512), 0, st, a);
+  d2r_attn_note(D2R_AV_X3_DKV);
   return 1;
 }
 

@@ -347,8 +347,9 @@ int d2r_mha_bwd(int dtype, const void* q, int64_t ldq, int64_t sqb, const void* 
  * 100/sqrt(768)) and the ContextRichCrossModalCell core (models/Cells.py:244-246, scale 1, residual Qs): three
  * launches (QK^T GEMM, softmax, PV GEMM) and an fp32 [B,Lq,Lk] round trip become one launch.
  * q/k/v/o/residual/dO/dq: bf16 [B, L, 768] views as (pointer, row stride, batch stride) in elements.
- * lse: fp32 [B, Lq].  d2r_xattn_bwd writes dq plus P and dS (bf16 [B, Lq, lkp], lkp = Lk rounded up to 8) for
- * the key-side products dV = P^T dO and dK = dS^T Q, which the caller runs as batched d2r_gemm (TN) launches.
+ * lse: fp32 [B, Lq].  d2r_xattn_bwd writes dq plus P and dS (16-bit [B, Lq, lkp]; lkp >= Lk, a multiple of 8, at most 640:
+ * columns >= Lk are scratch) for the key-side products dV = P^T dO and dK = dS^T Q, which the caller runs as batched d2r_gemm
+ * (TN) launches.  Pointers 16-byte aligned, strides multiples of 8 elements.  Deterministic.
  * ------------------------------------------------------------------------------------------------ */
 int d2r_xattn_supported(int dtype, int Lq, int Lk, int D);
 int d2r_xattn_fwd(int dtype, const void* q, int64_t ldq, int64_t sqb, const void* k, int64_t ldk, int64_t skb,
@@ -367,9 +368,11 @@ int d2r_xattn_bwd(int dtype, const void* q, int64_t ldq, int64_t sqb, const void
  * device pointers; h_residual may be NULL (or hold NULLs).  d2r_xattn_bwd_multi also runs the key-side products
  * dV = P^T dO and dK = dS^T Q of every sample and core (ONE grouped, batched launch of the LDS-DMA GEMM kernel when dk / dv
  * share their strides, e.g. the two halves of a packed k|v gradient), so it returns dq, dk and dv; h_P / h_dS are scratch
- * (16-bit [B, Lq, lkp] each, lkp = Lk rounded up to 8).  With h_o given (and Lk <= 256) the third-generation kernels run
+ * (16-bit [B, Lq, lkp] each; lkp >= Lk, a multiple of 8, at most 640; need not be initialised).  With h_o given, Lk <= 256,
+ * Lq <= 256 and lkp <= 256 the third-generation kernels run
  * (xattn3.hip: queries split over the waves, K / V streamed once through a six-slot LDS-DMA ring, D = rowsum(dO o (O - residual))
- * from the saved output); without it the second-generation query-side kernel, which recomputes D from P and dP. */
+ * from the saved output; dk / dv may then be 8-byte aligned with strides multiples of 4); otherwise the second-generation
+ * query-side kernel, which recomputes D from P and dP, and the TN launches. */
 int d2r_xattn_fwd_multi(int dtype, int ncore, const void* const* h_q, int64_t ldq, int64_t sqb, const void* const* h_k, int64_t ldk,
                         int64_t skb, const void* const* h_v, int64_t ldv, int64_t svb, void* const* h_o, int64_t ldo, int64_t sob,
                         const void* const* h_residual, int64_t ldr, int64_t srb, const float* mask, float* const* h_lse, int B, int Lq,

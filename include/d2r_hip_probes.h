@@ -31,6 +31,18 @@ void d2r_gemm_tuning(int nbuf, int vepi, int tile);
 int d2r_gemm_timer(int on);
 int d2r_gemm_timer_read(int* family, double* flops, double* bytes, float* ms, int capacity);
 
+/* Which attention kernel did a call take?  d2r_attn_trace(1) clears the record and arms it, d2r_attn_trace(0) disarms;
+ * d2r_attn_trace_read copies the variant codes of the attention kernels launched since arming, one per launch in launch order, and
+ * returns how many launches there were (codes == NULL: just the count; the record keeps the first 4096).  Host code only: disarmed it
+ * costs one predictable branch per launch.  Codes: MHA family * 10000 + head_dim * 100 + NK32 with family 1 / 2 = short forward /
+ * backward (NK32 = ceil(Lk / 32) forward, ceil(max(Lq, Lk) / 32) backward: the kernel's template argument) and 3 / 4 / 5 = long
+ * forward / long dQ / long dK-dV (NK32 = 0); single-head 768-wide cores 60001 xattn3 forward, 60002 xattn3 query-side backward,
+ * 60003 / 60004 full / compact product kernel (dV, dK, dQ), 60011 / 60012 / 60013 xattn2 forward <2,256> / <1,256> / <1,640>,
+ * 60021 / 60022 second-generation query-side backward <2> / <5>, 60031 its key side as one grouped batched TN launch, 60032 /
+ * 60033 as two (dV, then dK).  d2r_attn_trace_codes lists every code the library can record (returns their number). */
+void d2r_attn_trace(int on);
+int d2r_attn_trace_read(int* codes, int capacity);
+int d2r_attn_trace_codes(int* codes, int capacity);
 
 /* cycle stamps of workgroup 0 (measurement builds: D2R_GEMM_PROBES / D2R_G8_STAMPS / D2R_X3_PROBES=1 python -m d2r_amd.build) */
 void d2r_gemm_debug_stamps(unsigned long long* dst);    /* LDS-DMA 128-wide kernel: [waves][8] */
