@@ -187,6 +187,10 @@ SIGNATURES = {
     "d2r_patchify": (i32, [i32, vp, i32, i32, i32, i32, vp, vp]),
     "d2r_clip_preprocess_ws_bytes": (sz, [C.POINTER(ClipImageDesc), i32, i32]),
     "d2r_clip_preprocess": (i32, [vp, i64, C.POINTER(ClipImageDesc), vp, i32, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
+    "d2r_clip_cache_row_bytes": (sz, [i32]),
+    "d2r_clip_preprocess_u8": (i32, [vp, i64, C.POINTER(ClipImageDesc), vp, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, sz, vp]),
+    "d2r_clip_cache_gather": (i32, [vp, i64, vp, vp, i32, i32, vp, vp, vp]),
+    "d2r_gather_rows": (i32, [vp, vp, i64, i64, vp, vp, i32, vp]),
     "d2r_jpeg_decode_ws_bytes": (sz, [C.POINTER(JpegImageDesc), i32]),
     "d2r_jpeg_decode": (i32, [vp, i64, C.POINTER(JpegImageDesc), vp, i32, C.POINTER(JpegSegment), vp, i32, vp, vp, i64,
                               vp, i64, vp, vp, vp, sz, vp]),

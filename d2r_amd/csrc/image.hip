@@ -7,7 +7,14 @@
 // and clips (>> 22) to uint8.  An output pixel depends only on its own weights, so computing the crop alone is exact: pass 1 runs
 // on the source rows the crop rows' vertical support touches, S crop columns wide, into the workspace; pass 2 runs the vertical
 // weights over those rows and maps every (channel, uint8) pair through the normalisation table.
+//
+// The dataset cache (d2r_amd/cache.py) keeps pass 2's uint8 value instead of the table's: d2r_clip_preprocess_u8 writes the crop,
+// planar [3, S, S], into a row of a device-resident cache, and d2r_clip_cache_gather maps rows picked by index through the table
+// into the fp32 batch.  d2r_gather_rows does the same row pick for the token tensors.
 #include "common.h"
+
+#include <algorithm>
+#include <vector>
 
 namespace {
 
@@ -54,13 +61,18 @@ __global__ __launch_bounds__(256) void clip_hpass_kernel(const uint8_t* __restri
   }
 }
 
-// pass 2: out[b, c, i, j] = lut[c, clip8(sum_t ws[ymin_i - row0 + t, j, c] * ky_i[t])]
+// pass 2: out[b, c, i, j] = lut[c, clip8(sum_t ws[ymin_i - row0 + t, j, c] * ky_i[t])]; U8: the clip8 value itself, planar, into row
+// slots[b] of the cache (no table)
+template <bool U8>
 __global__ __launch_bounds__(256) void clip_vpass_kernel(const d2r_clip_image_desc* __restrict__ desc, const int32_t* __restrict__ tab,
                                                          const uint8_t* __restrict__ ws, const float* __restrict__ lut, int S,
-                                                         float* __restrict__ out) {
-  __shared__ float sl[3 * 256];
-  for (int i = threadIdx.x; i < 3 * 256; i += 256) sl[i] = lut[i];
-  __syncthreads();
+                                                         float* __restrict__ out, uint8_t* __restrict__ cache,
+                                                         const int64_t* __restrict__ slots, int64_t row_bytes) {
+  __shared__ float sl[U8 ? 1 : 3 * 256];
+  if constexpr (!U8) {
+    for (int i = threadIdx.x; i < 3 * 256; i += 256) sl[i] = lut[i];
+    __syncthreads();
+  }
   const d2r_clip_image_desc d = desc[blockIdx.y];
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= S * S) return;
@@ -77,10 +89,73 @@ __global__ __launch_bounds__(256) void clip_vpass_kernel(const d2r_clip_image_de
     a2 += (int)p[2] * w;
   }
   const int64_t plane = (int64_t)S * S;
-  float* o = out + (int64_t)blockIdx.y * 3 * plane + idx;
-  o[0] = sl[clip8(a0)];
-  o[plane] = sl[256 + clip8(a1)];
-  o[2 * plane] = sl[512 + clip8(a2)];
+  if constexpr (U8) {
+    uint8_t* o = cache + slots[blockIdx.y] * row_bytes + idx;
+    o[0] = (uint8_t)clip8(a0);
+    o[plane] = (uint8_t)clip8(a1);
+    o[2 * plane] = (uint8_t)clip8(a2);
+  } else {
+    float* o = out + (int64_t)blockIdx.y * 3 * plane + idx;
+    o[0] = sl[clip8(a0)];
+    o[plane] = sl[256 + clip8(a1)];
+    o[2 * plane] = sl[512 + clip8(a2)];
+  }
+}
+
+// out[b, c, i, j] = lut[c][cache[idx[b]][c, i, j]]: one 16-byte chunk of the cache row per thread, four 16-byte stores.  A chunk
+// that straddles two channels or the row's padding, or whose output is not 16-byte aligned (odd S), goes byte by byte.
+__global__ __launch_bounds__(256) void clip_cache_gather_kernel(const uint8_t* __restrict__ cache, int64_t row_bytes,
+                                                                const int64_t* __restrict__ idx, int S, const float* __restrict__ lut,
+                                                                float* __restrict__ out) {
+  __shared__ float sl[3 * 256];
+  for (int i = threadIdx.x; i < 3 * 256; i += 256) sl[i] = lut[i];
+  __syncthreads();
+  const int64_t row = idx[blockIdx.y];  // uniform: one scalar load per workgroup
+  const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
+  if (p0 >= row_bytes) return;
+  const int plane = S * S, n = 3 * plane;
+  const uint4 v = *reinterpret_cast<const uint4*>(cache + row * row_bytes + p0);
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  float* o = out + (int64_t)blockIdx.y * n + p0;
+  const int c = (int)(p0 / plane);
+  if (p0 + 16 <= n && (int)((p0 + 15) / plane) == c && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
+    const float* t = sl + c * 256;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      *reinterpret_cast<float4*>(o + 4 * q) =
+          make_float4(t[w[q] & 255u], t[(w[q] >> 8) & 255u], t[(w[q] >> 16) & 255u], t[w[q] >> 24]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int64_t p = p0 + q;
+      if (p < n) o[q] = sl[(int)(p / plane) * 256 + ((w[q >> 2] >> (8 * (q & 3))) & 255u)];
+    }
+  }
+}
+
+// dst[b] = src[idx[b]], rows of `elems` V-sized pieces
+template <typename V>
+__global__ __launch_bounds__(256) void gather_rows_kernel(V* __restrict__ dst, const V* __restrict__ src, int64_t elems,
+                                                          const int64_t* __restrict__ idx) {
+  const V* s = src + idx[blockIdx.y] * elems;
+  V* d = dst + (int64_t)blockIdx.y * elems;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < elems; e += (int64_t)gridDim.x * blockDim.x) d[e] = s[e];
+}
+
+template <typename V>
+int launch_gather_rows(void* dst, const void* src, int64_t row_bytes, const int64_t* idx, int B, hipStream_t st) {
+  const int64_t elems = row_bytes / (int64_t)sizeof(V);
+  const int block = elems <= 64 ? 64 : 256;
+  const int gx = (int)std::min<int64_t>(d2r_cdiv(elems, block), 1024);
+  hipLaunchKernelGGL(gather_rows_kernel<V>, dim3(gx, B), dim3(block), 0, st, (V*)dst, (const V*)src, elems, idx);
+  return d2r_check_launch("d2r_gather_rows");
+}
+
+// h[0..B) inside [0, rows)
+int check_rows(const char* who, const char* what, const int64_t* h, int B, int64_t rows) {
+  for (int b = 0; b < B; ++b)
+    D2R_REQUIRE(h[b] >= 0 && h[b] < rows, "%s: %s %d is %lld, outside the %lld rows", who, what, b, (long long)h[b], (long long)rows);
+  return D2R_OK;
 }
 
 // every bound the kernels rely on, checked on the host copies; *max_rows = the largest nrows
@@ -147,7 +222,65 @@ extern "C" int d2r_clip_preprocess(const uint8_t* src, int64_t src_bytes, const 
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(clip_hpass_kernel, dim3(d2r_cdiv(max_rows, HROWS), B), dim3(256), 0, st, src, desc, tab, S, (uint8_t*)ws);
   if (int rc = d2r_check_launch("d2r_clip_preprocess (horizontal pass)")) return rc;
-  hipLaunchKernelGGL(clip_vpass_kernel, dim3(d2r_cdiv((int64_t)S * S, 256), B), dim3(256), 0, st, desc, tab, (const uint8_t*)ws, lut,
-                     S, out);
+  hipLaunchKernelGGL(clip_vpass_kernel<false>, dim3(d2r_cdiv((int64_t)S * S, 256), B), dim3(256), 0, st, desc, tab,
+                     (const uint8_t*)ws, lut, S, out, (uint8_t*)nullptr, (const int64_t*)nullptr, (int64_t)0);
   return d2r_check_launch("d2r_clip_preprocess (vertical pass)");
+}
+
+extern "C" size_t d2r_clip_cache_row_bytes(int S) { return S < 1 ? 0 : ((size_t)3 * S * S + 15) / 16 * 16; }
+
+extern "C" int d2r_clip_preprocess_u8(const uint8_t* src, int64_t src_bytes, const d2r_clip_image_desc* h_desc,
+                                      const d2r_clip_image_desc* desc, int B, int S, const int32_t* h_tab, const int32_t* tab,
+                                      int64_t tab_len, uint8_t* cache, int64_t cache_rows, const int64_t* h_slots, const int64_t* slots,
+                                      void* ws, size_t ws_bytes, void* stream) {
+  D2R_REQUIRE(src && h_desc && desc && h_tab && tab && cache && h_slots && slots && ws, "d2r_clip_preprocess_u8: null pointer");
+  D2R_REQUIRE(B >= 1 && B <= 65535 && S >= 1 && S <= 4096 && tab_len >= 0 && tab_len <= INT32_MAX && cache_rows >= 1,
+              "d2r_clip_preprocess_u8: bad batch %d, crop size %d, table length %lld or %lld cache rows", B, S, (long long)tab_len,
+              (long long)cache_rows);
+  D2R_REQUIRE((reinterpret_cast<uintptr_t>(desc) & 7u) == 0 && (reinterpret_cast<uintptr_t>(tab) & 3u) == 0 &&
+                  (reinterpret_cast<uintptr_t>(slots) & 7u) == 0,
+              "d2r_clip_preprocess_u8: desc / slots must be 8-byte, tab 4-byte aligned");
+  if (int rc = check_rows("d2r_clip_preprocess_u8", "slot", h_slots, B, cache_rows)) return rc;
+  std::vector<int64_t> sorted(h_slots, h_slots + B);
+  std::sort(sorted.begin(), sorted.end());
+  for (int b = 1; b < B; ++b)
+    D2R_REQUIRE(sorted[b] != sorted[b - 1], "d2r_clip_preprocess_u8: slot %lld is named twice in one call", (long long)sorted[b]);
+  int max_rows = 0;
+  if (int rc = check_descs(h_desc, B, S, src_bytes, h_tab, tab_len, ws_bytes, &max_rows)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(clip_hpass_kernel, dim3(d2r_cdiv(max_rows, HROWS), B), dim3(256), 0, st, src, desc, tab, S, (uint8_t*)ws);
+  if (int rc = d2r_check_launch("d2r_clip_preprocess_u8 (horizontal pass)")) return rc;
+  hipLaunchKernelGGL(clip_vpass_kernel<true>, dim3(d2r_cdiv((int64_t)S * S, 256), B), dim3(256), 0, st, desc, tab, (const uint8_t*)ws,
+                     (const float*)nullptr, S, (float*)nullptr, cache, slots, (int64_t)d2r_clip_cache_row_bytes(S));
+  return d2r_check_launch("d2r_clip_preprocess_u8 (vertical pass)");
+}
+
+extern "C" int d2r_clip_cache_gather(const uint8_t* cache, int64_t cache_rows, const int64_t* h_idx, const int64_t* idx, int B, int S,
+                                     const float* lut, float* out, void* stream) {
+  D2R_REQUIRE(cache && h_idx && idx && lut && out, "d2r_clip_cache_gather: null pointer");
+  D2R_REQUIRE(B >= 1 && B <= 65535 && S >= 1 && S <= 4096 && cache_rows >= 1, "d2r_clip_cache_gather: bad batch %d, crop size %d or %lld cache rows",
+              B, S, (long long)cache_rows);
+  D2R_REQUIRE(d2r_aligned16(cache) && (reinterpret_cast<uintptr_t>(idx) & 7u) == 0 && (reinterpret_cast<uintptr_t>(lut) & 3u) == 0 &&
+                  (reinterpret_cast<uintptr_t>(out) & 3u) == 0,
+              "d2r_clip_cache_gather: cache must be 16-byte, idx 8-byte, lut / out 4-byte aligned");
+  if (int rc = check_rows("d2r_clip_cache_gather", "index", h_idx, B, cache_rows)) return rc;
+  const int64_t row_bytes = (int64_t)d2r_clip_cache_row_bytes(S);
+  hipLaunchKernelGGL(clip_cache_gather_kernel, dim3(d2r_cdiv(row_bytes / 16, 256), B), dim3(256), 0, (hipStream_t)stream, cache, row_bytes,
+                     idx, S, lut, out);
+  return d2r_check_launch("d2r_clip_cache_gather");
+}
+
+extern "C" int d2r_gather_rows(void* dst, const void* src, int64_t src_rows, int64_t row_bytes, const int64_t* h_idx, const int64_t* idx,
+                               int B, void* stream) {
+  D2R_REQUIRE(dst && src && h_idx && idx, "d2r_gather_rows: null pointer");
+  D2R_REQUIRE(B >= 1 && B <= 65535 && src_rows >= 1 && row_bytes >= 1, "d2r_gather_rows: bad batch %d, %lld source rows or %lld bytes per row", B,
+              (long long)src_rows, (long long)row_bytes);
+  D2R_REQUIRE((reinterpret_cast<uintptr_t>(idx) & 7u) == 0, "d2r_gather_rows: idx must be 8-byte aligned");
+  if (int rc = check_rows("d2r_gather_rows", "index", h_idx, B, src_rows)) return rc;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src) | (uintptr_t)row_bytes;
+  hipStream_t st = (hipStream_t)stream;
+  if ((bits & 15u) == 0) return launch_gather_rows<uint4>(dst, src, row_bytes, idx, B, st);
+  if ((bits & 7u) == 0) return launch_gather_rows<uint2>(dst, src, row_bytes, idx, B, st);
+  if ((bits & 3u) == 0) return launch_gather_rows<uint32_t>(dst, src, row_bytes, idx, B, st);
+  return launch_gather_rows<uint8_t>(dst, src, row_bytes, idx, B, st);
 }

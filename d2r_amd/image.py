@@ -15,6 +15,8 @@ multiply-add): a pairwise sum, or the same arithmetic contracted to FMA on the d
 The loader side (``ClipCollate``) packs a batch of decoded images into ``PackedImages``: one uint8 buffer of the pixels and one
 buffer of descriptors + weight tables; ``PackedImages.to_pixel_values(device)`` copies both (non-blocking from pinned memory) and
 launches the kernels on the current stream.  ``reference_preprocess`` is the same computation in numpy (tests, CPU checks).
+``to_cache`` stops one step earlier: the uint8 crop goes into rows of a device-resident cache (``d2r_clip_preprocess_u8``), from
+which ``clip_cache_gather`` later builds the same pixel values by index (d2r_amd.cache, --cache_dataset device).
 """
 from __future__ import annotations
 
@@ -206,6 +208,85 @@ def clip_preprocess(pixels: torch.Tensor, h_desc: np.ndarray, desc: torch.Tensor
     return out
 
 
+def cache_row_bytes(S: int) -> int:
+    """Bytes of one row of a crop cache: the planar uint8 [3, S, S] crop, padded to a multiple of 16."""
+    return int(_lib.load().d2r_clip_cache_row_bytes(S))
+
+
+def clip_preprocess_u8(pixels: torch.Tensor, h_desc: np.ndarray, desc: torch.Tensor, h_tab: torch.Tensor, tab: torch.Tensor, S: int,
+                       cache: torch.Tensor, h_slots: torch.Tensor, slots: torch.Tensor, ws: torch.Tensor = None) -> None:
+    """d2r_clip_preprocess_u8 on the current stream: image b's uint8 crop, planar [3, S, S], into row slots[b] of `cache` (uint8
+    [rows, cache_row_bytes(S)] on the device).  h_slots (host) and slots (device) are int64 [B]; the library checks every bound on
+    the host copies before it enqueues anything."""
+    B = len(h_desc)
+    dev = pixels.device
+    if not (pixels.dtype == torch.uint8 and desc.dtype == torch.uint8 and tab.dtype == torch.int32 and cache.dtype == torch.uint8 and
+            h_slots.dtype == torch.int64 and slots.dtype == torch.int64):
+        raise TypeError("pixels / desc / cache uint8, tab int32, slots int64 expected")
+    if h_desc.dtype != DESC_DTYPE or desc.numel() != B * DESC_DTYPE.itemsize or h_tab.numel() != tab.numel() or \
+            h_slots.numel() != B or slots.numel() != B or cache.dim() != 2 or cache.shape[1] != cache_row_bytes(S):
+        raise ValueError("descriptor / table / slot / cache sizes disagree")
+    if not all(t.is_cuda and t.device == dev and t.is_contiguous() for t in (desc, tab, cache, slots)) or h_tab.is_cuda or \
+            not h_tab.is_contiguous() or h_slots.is_cuda or not h_slots.is_contiguous():
+        raise ValueError("device tensors must be contiguous on one GPU, h_tab / h_slots on the host")
+    hd = C.cast(h_desc.ctypes.data, C.POINTER(_lib.ClipImageDesc))
+    if ws is None:
+        ws = torch.empty(max(int(_lib.load().d2r_clip_preprocess_ws_bytes(hd, B, S)), 1), dtype=torch.uint8, device=dev)
+    from .functional import _stream
+    _lib.call("d2r_clip_preprocess_u8", pixels.data_ptr(), pixels.numel(), hd, desc.data_ptr(), B, S, h_tab.data_ptr(), tab.data_ptr(),
+              tab.numel(), cache.data_ptr(), cache.shape[0], h_slots.data_ptr(), slots.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+
+
+def clip_cache_gather(cache: torch.Tensor, h_idx: torch.Tensor, idx: torch.Tensor, S: int, lut: torch.Tensor,
+                      out: torch.Tensor = None) -> torch.Tensor:
+    """d2r_clip_cache_gather on the current stream: fp32 [B, 3, S, S] pixel values of the cache rows idx (int64 [B] on the device,
+    h_idx its host copy; repeats allowed)."""
+    B = h_idx.numel()
+    dev = cache.device
+    if not (cache.dtype == torch.uint8 and h_idx.dtype == torch.int64 and idx.dtype == torch.int64 and lut.dtype == torch.float32):
+        raise TypeError("cache uint8, idx int64, lut float32 expected")
+    if cache.dim() != 2 or cache.shape[1] != cache_row_bytes(S) or idx.numel() != B or lut.numel() != 768:
+        raise ValueError("cache / index / lut sizes disagree")
+    if not all(t.is_cuda and t.device == dev and t.is_contiguous() for t in (cache, idx, lut)) or h_idx.is_cuda or not h_idx.is_contiguous():
+        raise ValueError("device tensors must be contiguous on one GPU, h_idx on the host")
+    if out is None:
+        out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * 3 * S * S or out.device != dev:
+        raise ValueError("out must be a contiguous fp32 [B, 3, S, S] tensor on the cache's device")
+    from .functional import _stream
+    _lib.call("d2r_clip_cache_gather", cache.data_ptr(), cache.shape[0], h_idx.data_ptr(), idx.data_ptr(), B, S, lut.data_ptr(),
+              out.data_ptr(), _stream())
+    return out
+
+
+def gather_rows(src: torch.Tensor, h_idx: torch.Tensor, idx: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """d2r_gather_rows on the current stream: out[b] = src[idx[b]] for a contiguous device tensor src [N, ...] (idx int64 [B] on
+    the device, h_idx its host copy)."""
+    B = h_idx.numel()
+    if not (src.is_cuda and src.is_contiguous() and src.dim() >= 1 and src.shape[0] >= 1):
+        raise ValueError("src must be a contiguous device tensor with at least one row")
+    if not (h_idx.dtype == torch.int64 and idx.dtype == torch.int64 and idx.numel() == B and idx.is_cuda and idx.device == src.device and
+            idx.is_contiguous() and not h_idx.is_cuda and h_idx.is_contiguous()):
+        raise ValueError("idx must be a contiguous int64 tensor on src's device, h_idx its host copy")
+    if out is None:
+        out = torch.empty((B,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    elif out.dtype != src.dtype or not out.is_contiguous() or out.device != src.device or out.numel() * src.shape[0] != B * src.numel():
+        raise ValueError("out must be a contiguous [B, ...] tensor of src's dtype on its device")
+    row_bytes = src.numel() // src.shape[0] * src.element_size()
+    from .functional import _stream
+    _lib.call("d2r_gather_rows", out.data_ptr(), src.data_ptr(), src.shape[0], row_bytes, h_idx.data_ptr(), idx.data_ptr(), B, _stream())
+    return out
+
+
+def _crops_to_cache(pixels, clip_meta, batch, S, cache, h_slots):
+    """Shared tail of PackedImages.to_cache / PackedJpegImages.to_cache: `pixels` are the batch's source pixels on the device."""
+    nd = batch * DESC_DTYPE.itemsize
+    meta = clip_meta.to(pixels.device, non_blocking=True)
+    h_desc = clip_meta.numpy()[:nd].view(DESC_DTYPE)
+    clip_preprocess_u8(pixels, h_desc, meta[:nd], clip_meta[nd:].view(torch.int32), meta[nd:].view(torch.int32), S, cache, h_slots,
+                       h_slots.to(pixels.device, non_blocking=True))
+
+
 class PackedImages:
     """A collated batch of decoded images: the loader element the trainer turns into pixel values on the device.
     ``pixels`` uint8 [N] (HWC RGB images back to back), ``meta`` uint8 [B * 72 + 4 * T] (descriptors, then the int32 table)."""
@@ -240,6 +321,11 @@ class PackedImages:
         nd = self.batch * DESC_DTYPE.itemsize
         return clip_preprocess(pixels, h_desc, meta[:nd], h_tab, meta[nd:].view(torch.int32), self.S,
                                _device_table(str(pixels.device), self.norm))
+
+    def to_cache(self, device, cache: torch.Tensor, h_slots: torch.Tensor) -> None:
+        """The batch's uint8 crops into rows h_slots (host int64 [B]) of the crop cache on `device`: the copies of
+        to_pixel_values, then d2r_clip_preprocess_u8."""
+        _crops_to_cache(self.pixels.to(device, non_blocking=True), self.meta, self.batch, self.S, cache, h_slots)
 
     def to_pixel_values_cpu(self) -> torch.Tensor:
         """The same batch through the numpy restatement (reference_preprocess): fp32 [B, 3, S, S] on the host."""

@@ -629,15 +629,23 @@ class PackedJpegImages:
         return clip_preprocess(pixels, h_desc, meta[:nd], self.clip_meta[nd:].view(torch.int32), meta[nd:].view(torch.int32), self.S,
                                _device_table(str(pixels.device), self.norm))
 
+    def to_cache(self, device, cache: torch.Tensor, h_slots: torch.Tensor) -> None:
+        """d2r_jpeg_decode, then d2r_clip_preprocess_u8: the batch's uint8 crops into rows h_slots (host int64 [B]) of the crop
+        cache on `device` (d2r_amd.cache); ``self.status`` as after to_pixel_values."""
+        from .image import _crops_to_cache
+        _crops_to_cache(self.decode(device), self.clip_meta, self.batch, self.S, cache, h_slots)
+
 
 class DecodeLog:
     """Counts, per epoch, the images decoded on the device and on the host and the device decodes with a nonzero status.  The
-    status tensors are only read in ``poll()``, which the trainer calls right after a host sync it makes anyway."""
+    status tensors are only read in ``poll()``, which the trainer calls right after a host sync it makes anyway.  Batches served
+    from the device cache (d2r_amd.cache.CachedBatch) decode nothing and are counted by their ``cached_images``."""
 
     def __init__(self, logger):
-        self.logger, self.device, self.host, self.bad, self.pending = logger, 0, 0, 0, []
+        self.logger, self.device, self.host, self.bad, self.pending, self.cached = logger, 0, 0, 0, [], 0
 
     def note(self, batch):
+        self.cached += getattr(batch, "cached_images", 0)
         for t in batch:
             if isinstance(t, PackedJpegImages):
                 self.device += t.n_device
@@ -662,4 +670,6 @@ class DecodeLog:
         if self.device or self.host:
             self.logger.info("%s images: %d decoded on the device, %d on the host, %d device decode(s) with corrupt data", what,
                              self.device, self.host, self.bad)
-        self.device = self.host = self.bad = 0
+        if self.cached:
+            self.logger.info("%s images: %d images from the device cache", what, self.cached)
+        self.device = self.host = self.bad = self.cached = 0

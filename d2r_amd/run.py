@@ -11,6 +11,7 @@ of --bert_name / --vit_name (local directories) as the reference does (run.py:12
 
 --only_test --load_path <best_model.pth> predicts the test split with a saved checkpoint (no training; unlabelled test entries
 allowed), --write_path writes the per-sample predictions as JSON Lines (MSDTrainer.predict); both are single-process.
+--cache_dataset device (with --data_path) decodes every split once and serves all later batches from device memory (d2r_amd.cache).
 """
 from __future__ import annotations
 
@@ -110,6 +111,9 @@ def build_parser():
     p.add_argument("--image_decode", default="host", choices=["host", "device"], help="with --data_path: decode the JPEG files in "
                    "the loader workers with Pillow (host), or only parse them there and decode them on the GPU, bit-identically "
                    "(device; files the device path does not take, e.g. progressive JPEGs, are still decoded on the host)")
+    p.add_argument("--cache_dataset", default="off", choices=["off", "device"], help="with --data_path: decode and resize every "
+                   "image once, keep the uint8 crops and the token tensors of every split in device memory (150,528 bytes per image "
+                   "at 224 x 224) and build every batch there by index; the run takes the same steps as without it (d2r_amd.cache)")
     p.add_argument("--pretrained", action="store_true", help="model configs, weights and image preprocessing from the local "
                    "--bert_name / --vit_name checkpoints (BertModel, CLIPModel.vision_model, preprocessor_config.json)")
     return p
@@ -146,6 +150,8 @@ def main(argv=None):
         raise SystemExit("--only_test needs --load_path (the checkpoint to evaluate)")
     if (args.only_test or args.write_path is not None) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("--only_test / --write_path run in a single process: start without torch.distributed.run (WORLD_SIZE 1)")
+    if args.cache_dataset != "off" and args.data_path is None:
+        raise SystemExit("--cache_dataset device caches the files of --data_path: synthetic data has nothing to decode; run without it")
     from .config import TextConfig, VisionConfig
     from .data import MSDDataset, SyntheticMSDDataset, make_loader
     from .image import CLIP_MEAN, CLIP_STD, RESCALE, ClipCollate, processor_settings
@@ -200,6 +206,13 @@ def main(argv=None):
     if not args.only_test:
         train_dl, dev_dl = loader(args.train_samples, 1, True, 0), loader(args.eval_samples, 2, False, 1)
     test_dl = loader(args.eval_samples, 3, False, 2)
+    if args.cache_dataset == "device" and args.only_test:
+        logger.info("--cache_dataset device is ignored with --only_test: a single pass over the test split gains nothing")
+    elif args.cache_dataset == "device":
+        # every rank caches the whole of each split (the training shards change every epoch); the default generator is untouched
+        from .cache import cache_loaders
+        cached = cache_loaders({"train": train_dl, "dev": dev_dl, "test": test_dl}, args.device, logger)
+        train_dl, dev_dl, test_dl = cached["train"], cached["dev"], cached["test"]
     model = UnimoModelF(args=args, vision_config=vision_config, text_config=text_config, num_classes=args.num_classes)
     if args.only_test:
         trainer = MSDTrainer(test_data=test_dl, model=model, args=args, logger=logger, writer=None)

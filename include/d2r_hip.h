@@ -592,6 +592,31 @@ size_t d2r_clip_preprocess_ws_bytes(const d2r_clip_image_desc* h_desc, int B, in
 int d2r_clip_preprocess(const uint8_t* src, int64_t src_bytes, const d2r_clip_image_desc* h_desc, const d2r_clip_image_desc* desc,
                         int B, int S, const int32_t* h_tab, const int32_t* tab, int64_t tab_len, const float* lut, float* out,
                         void* ws, size_t ws_bytes, void* stream);
+/* K20  Device-resident dataset cache (d2r_amd/cache.py, --cache_dataset device): the uint8 crop the vertical pass of
+ * d2r_clip_preprocess feeds to lut is a lossless cache entry (the pixel values are a function of it and the channel alone).
+ * A cache is uint8 [cache_rows, d2r_clip_cache_row_bytes(S)], 16-byte aligned; a row holds one image's crop, planar [3, S, S], and
+ * padding up to a multiple of 16 bytes (3 * S * S rounded up) that nothing reads as pixels.
+ *
+ * d2r_clip_preprocess_u8: d2r_clip_preprocess without the table - same src / desc / tab / ws and the same two passes, image b's crop
+ * written to cache row slots[b] (the row's padding is left alone).  h_slots is the host copy of slots (int64 [B]): every slot must
+ * lie in [0, cache_rows) and be named once per call; together with the descriptor checks of d2r_clip_preprocess this is verified
+ * before anything is enqueued, and a refused call writes nothing.
+ *
+ * d2r_clip_cache_gather: out[b, c, i, j] = lut[c][cache[idx[b]][c, i, j]], fp32 [B, 3, S, S], OVERWRITTEN - bit for bit what
+ * d2r_clip_preprocess writes for the same images (what d2r_patchify consumes).  Indices may repeat; h_idx is the host copy of idx
+ * (int64 [B]) and an index outside [0, cache_rows) is refused before the launch.
+ *
+ * d2r_gather_rows: dst[b][0..row_bytes) = src[h_idx[b]][0..row_bytes) for b < B, rows of src and dst back to back (the token ids,
+ * masks, segment ids and labels of a cached batch).  16-byte accesses when dst, src and row_bytes are multiples of 16, otherwise
+ * 8-, 4- or 1-byte ones.  An index outside [0, src_rows) is refused before the launch; dst must not overlap src. */
+size_t d2r_clip_cache_row_bytes(int S);
+int d2r_clip_preprocess_u8(const uint8_t* src, int64_t src_bytes, const d2r_clip_image_desc* h_desc, const d2r_clip_image_desc* desc,
+                           int B, int S, const int32_t* h_tab, const int32_t* tab, int64_t tab_len, uint8_t* cache,
+                           int64_t cache_rows, const int64_t* h_slots, const int64_t* slots, void* ws, size_t ws_bytes, void* stream);
+int d2r_clip_cache_gather(const uint8_t* cache, int64_t cache_rows, const int64_t* h_idx, const int64_t* idx, int B, int S,
+                          const float* lut, float* out, void* stream);
+int d2r_gather_rows(void* dst, const void* src, int64_t src_rows, int64_t row_bytes, const int64_t* h_idx, const int64_t* idx, int B,
+                    void* stream);
 /* K19  Baseline JPEG decoding of a batch of images on the device (processor/dataset.py:89: Image.open(p).convert("RGB") in the
  * reference's loader workers), bit-identical to libjpeg-turbo's default path as Pillow uses it: Huffman decoding, ISLOW IDCT with
  * its range-limit table, fancy h2v1 / h2v2 chroma upsampling, fixed-point YCbCr -> RGB.  The host (d2r_amd/jpeg.py) parses the
