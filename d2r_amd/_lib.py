@@ -201,6 +201,9 @@ SIGNATURES = {
     "d2r_grad_nonfinite": (i32, [vp, i64, vp, vp]),
     "d2r_adamw_step_clip": (i32, [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, i64, f32, vp, vp, vp]),
     "d2r_adamw_step_dev_clip": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, f32, f32, f32, f32, vp, vp, vp]),
+    "d2r_adamw_step_ema": (i32, [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, i64, f32, vp, vp, vp, f32, vp]),
+    "d2r_adamw_step_dev_ema": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp]),
+    "d2r_swap_f32": (i32, [vp, vp, i64, vp]),
     "d2r_grad_sumsq": (i32, [vp, vp, i32, vp, i64, vp]),
     "d2r_grad_norm_finish": (i32, [vp, i64, f32, vp, f32, vp, vp, vp]),
     "d2r_copy_rows": (i32, [vp, i64, vp, i64, i64, i64, vp]),

@@ -353,13 +353,17 @@ __device__ __forceinline__ void st4(float* p, const Pack<float, 4>& v) {
 
 // CLIP: the gradient is also multiplied by the clipping coefficient *d_coef (d2r_grad_norm_finish), AFTER the unscale, as
 // clip_grad_norm_ multiplies the already unscaled gradient: (g * gscale) * coef, two roundings.  CLIP = false is the plain step.
-template <typename H, bool NT, bool CLIP>
+// EMA: an exponential moving average of the weights rides along as one more fp32 stream, e += omd * (w_new - e) with
+// omd = 1 - decay_t (by value, or *d_omd in the hipGraph form) and w_new the weight this thread has just computed; a dropped step
+// leaves it alone like w, m and v.  EMA = false is the step without it: nothing of ema / omd / d_omd is read.
+template <typename H, bool NT, bool CLIP, bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ w, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     H* __restrict__ w16, int64_t n, float lr, float b1, float b2,
                                                     float eps, float wd, float bc1, float bc2_sqrt, float gscale,
                                                     const float* __restrict__ d_hyper, const int* __restrict__ d_skip,
-                                                    const float* __restrict__ d_coef) {
+                                                    const float* __restrict__ d_coef, float* __restrict__ ema, float omd,
+                                                    const float* __restrict__ d_omd) {
   if (d_skip && *d_skip) return;  // overflowed loss-scaled gradients: this step is dropped
   if (d_hyper) {  // hipGraph-safe variant: per-step scalars live in device memory, refreshed before each replay
     lr = d_hyper[0];
@@ -369,6 +373,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ w, const
   }
   float coef = 1.f;
   if constexpr (CLIP) coef = *d_coef;
+  if constexpr (EMA) {
+    if (d_omd) omd = *d_omd;
+  }
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
   const int64_t n4 = n / 4;
@@ -389,6 +396,12 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ w, const
     st4<NT>(w + k * 4, pw);
     st4<NT>(m + k * 4, pm);
     st4<NT>(v + k * 4, pv);
+    if constexpr (EMA) {
+      Pack<float, 4> pe = ld4<NT>(ema + k * 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) pe.v[j] += omd * (pw.v[j] - pe.v[j]);
+      st4<NT>(ema + k * 4, pe);
+    }
     if (w16) {
       Pack<H, 4> ph;
 #pragma unroll
@@ -402,6 +415,15 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ w, const
     w[e] = wi; m[e] = mi; v[e] = vi;
     if (w16) w16[e] = (H)wi;
   }
+  if constexpr (EMA) {
+    // The tail's average (at most 3 elements of the launch) in a loop of its own, reading back the weight this thread has just
+    // stored: with these operations inside the loop above the compiler packs pairs of upd()'s scalar multiplies and adds instead of
+    // fusing them as it does in the plain kernel, and w, m, v must equal the plain step bit for bit (tests/test_gpu_ema.py).
+    for (int64_t e = n4 * 4 + tid; e < n; e += nthreads) {
+      const float ei = ema[e];
+      ema[e] = ei + omd * (w[e] - ei);
+    }
+  }
 }
 
 static int g_adamw_nt = 0, g_adamw_blocks = 0;  // A/B (include/d2r_hip_probes.h): non-temporal loads / stores, grid cap
@@ -409,27 +431,32 @@ extern "C" void d2r_adamw_probe_mode(int nt, int blocks) { g_adamw_nt = nt, g_ad
 
 static int adamw_launch(const char* name, float* w, const float* g, float* m, float* v, void* w16, int w16_dtype, int64_t n, float lr,
                         float b1, float b2, float eps, float wd, float bc1, float bc2s, float gscale, const float* d_hyper,
-                        const int* d_skip, const float* d_coef, void* stream) {
+                        const int* d_skip, const float* d_coef, float* ema, float omd, const float* d_omd, void* stream) {
   D2R_REQUIRE(d2r_aligned16(w) && d2r_aligned16(g) && d2r_aligned16(m) && d2r_aligned16(v), "%s: pointers must be 16-byte aligned", name);
   D2R_REQUIRE(!w16 || ((reinterpret_cast<uintptr_t>(w16) & 7u) == 0 && d2r_is16(w16_dtype)),
               "%s: the 16-bit shadow must be 8-byte aligned and D2R_BF16 or D2R_F16 (got dtype %d)", name, w16_dtype);
+  D2R_REQUIRE(!ema || d2r_aligned16(ema), "%s: the EMA buffer must be 16-byte aligned", name);
   if (n == 0) return D2R_OK;
   int blocks = (int)((n / 4 + 256) / 256);
   const int cap = g_adamw_blocks > 0 ? g_adamw_blocks : 2048;
   if (blocks > cap) blocks = cap;
-#define D2R_ADAMW_LAUNCH(H, NT, CLIP) \
-  hipLaunchKernelGGL((adamw_kernel<H, NT, CLIP>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, g, m, v, (H*)w16, n, lr, b1, b2, eps, wd, \
-                     bc1, bc2s, gscale, d_hyper, d_skip, d_coef)
-#define D2R_ADAMW_LAUNCH_NT(H, CLIP)       \
-  if (g_adamw_nt) D2R_ADAMW_LAUNCH(H, true, CLIP); \
-  else D2R_ADAMW_LAUNCH(H, false, CLIP)
+#define D2R_ADAMW_LAUNCH(H, NT, CLIP, EMA) \
+  hipLaunchKernelGGL((adamw_kernel<H, NT, CLIP, EMA>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, g, m, v, (H*)w16, n, lr, b1, b2, eps, \
+                     wd, bc1, bc2s, gscale, d_hyper, d_skip, d_coef, ema, omd, d_omd)
+#define D2R_ADAMW_LAUNCH_NT(H, CLIP, EMA)       \
+  if (g_adamw_nt) D2R_ADAMW_LAUNCH(H, true, CLIP, EMA); \
+  else D2R_ADAMW_LAUNCH(H, false, CLIP, EMA)
+#define D2R_ADAMW_LAUNCH_EMA(H, CLIP)       \
+  if (ema) { D2R_ADAMW_LAUNCH_NT(H, CLIP, true); } \
+  else { D2R_ADAMW_LAUNCH_NT(H, CLIP, false); }
   if (w16 && w16_dtype == D2R_F16) {
-    if (d_coef) { D2R_ADAMW_LAUNCH_NT(f16_t, true); }
-    else { D2R_ADAMW_LAUNCH_NT(f16_t, false); }
+    if (d_coef) { D2R_ADAMW_LAUNCH_EMA(f16_t, true) }
+    else { D2R_ADAMW_LAUNCH_EMA(f16_t, false) }
   } else {
-    if (d_coef) { D2R_ADAMW_LAUNCH_NT(bf16_t, true); }
-    else { D2R_ADAMW_LAUNCH_NT(bf16_t, false); }
+    if (d_coef) { D2R_ADAMW_LAUNCH_EMA(bf16_t, true) }
+    else { D2R_ADAMW_LAUNCH_EMA(bf16_t, false) }
   }
+#undef D2R_ADAMW_LAUNCH_EMA
 #undef D2R_ADAMW_LAUNCH_NT
 #undef D2R_ADAMW_LAUNCH
   return d2r_check_launch(name);
@@ -443,7 +470,7 @@ extern "C" int d2r_adamw_step(float* w, const float* g, float* m, float* v, void
   const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
   const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   return adamw_launch("d2r_adamw_step", w, g, m, v, w16, w16_dtype, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale,
-                      nullptr, d_skip, nullptr, stream);
+                      nullptr, d_skip, nullptr, nullptr, 0.f, nullptr, stream);
 }
 
 // the eager step with gradient clipping: d_coef = the coefficient d2r_grad_norm_finish wrote (device float)
@@ -454,7 +481,7 @@ extern "C" int d2r_adamw_step_clip(float* w, const float* g, float* m, float* v,
   const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
   const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   return adamw_launch("d2r_adamw_step_clip", w, g, m, v, w16, w16_dtype, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale,
-                      nullptr, d_skip, d_coef, stream);
+                      nullptr, d_skip, d_coef, nullptr, 0.f, nullptr, stream);
 }
 
 // hipGraph-capturable form: d_hyper = device float[4] {lr, 1-beta1^t, sqrt(1-beta2^t), grad_scale}
@@ -463,14 +490,68 @@ extern "C" int d2r_adamw_step_dev(float* w, const float* g, float* m, float* v, 
                                   const int* d_skip, void* stream) {
   D2R_REQUIRE(w && g && m && v && d_hyper && n >= 0, "d2r_adamw_step_dev: bad arguments");
   return adamw_launch("d2r_adamw_step_dev", w, g, m, v, w16, w16_dtype, n, 0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, 1.f, d_hyper,
-                      d_skip, nullptr, stream);
+                      d_skip, nullptr, nullptr, 0.f, nullptr, stream);
 }
 extern "C" int d2r_adamw_step_dev_clip(float* w, const float* g, float* m, float* v, void* w16, int w16_dtype, int64_t n,
                                        const float* d_hyper, float beta1, float beta2, float eps, float weight_decay,
                                        const int* d_skip, const float* d_coef, void* stream) {
   D2R_REQUIRE(w && g && m && v && d_hyper && d_coef && n >= 0, "d2r_adamw_step_dev_clip: bad arguments");
   return adamw_launch("d2r_adamw_step_dev_clip", w, g, m, v, w16, w16_dtype, n, 0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, 1.f,
-                      d_hyper, d_skip, d_coef, stream);
+                      d_hyper, d_skip, d_coef, nullptr, 0.f, nullptr, stream);
+}
+
+// the two steps above with the weight EMA riding along (d_coef optional: clipping and EMA compose): ema = fp32 shadow laid out
+// like w, ema_one_minus_decay = 1 - decay_t, computed by the caller in double and rounded once
+extern "C" int d2r_adamw_step_ema(float* w, const float* g, float* m, float* v, void* w16, int w16_dtype, int64_t n, float lr,
+                                  float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                                  const int* d_skip, const float* d_coef, float* ema, float ema_one_minus_decay, void* stream) {
+  D2R_REQUIRE(w && g && m && v && n >= 0 && step >= 1, "d2r_adamw_step_ema: bad arguments");
+  D2R_REQUIRE(ema && ema != w, "d2r_adamw_step_ema: ema must be a buffer of its own (not NULL, not w)");
+  D2R_REQUIRE(ema_one_minus_decay >= 0.f && ema_one_minus_decay <= 1.f, "d2r_adamw_step_ema: 1 - decay = %g is outside [0, 1]",
+              (double)ema_one_minus_decay);
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  return adamw_launch("d2r_adamw_step_ema", w, g, m, v, w16, w16_dtype, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale,
+                      nullptr, d_skip, d_coef, ema, ema_one_minus_decay, nullptr, stream);
+}
+// hipGraph-capturable: the factor is read from the device float d_ema_one_minus_decay (d_hyper[4] keeps its layout)
+extern "C" int d2r_adamw_step_dev_ema(float* w, const float* g, float* m, float* v, void* w16, int w16_dtype, int64_t n,
+                                      const float* d_hyper, float beta1, float beta2, float eps, float weight_decay,
+                                      const int* d_skip, const float* d_coef, float* ema, const float* d_ema_one_minus_decay,
+                                      void* stream) {
+  D2R_REQUIRE(w && g && m && v && d_hyper && n >= 0, "d2r_adamw_step_dev_ema: bad arguments");
+  D2R_REQUIRE(ema && ema != w, "d2r_adamw_step_dev_ema: ema must be a buffer of its own (not NULL, not w)");
+  D2R_REQUIRE(d_ema_one_minus_decay, "d2r_adamw_step_dev_ema: d_ema_one_minus_decay is NULL");
+  return adamw_launch("d2r_adamw_step_dev_ema", w, g, m, v, w16, w16_dtype, n, 0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, 1.f,
+                      d_hyper, d_skip, d_coef, ema, 0.f, d_ema_one_minus_decay, stream);
+}
+
+// ---- a[i] <-> b[i] over two disjoint fp32 ranges in one pass (evaluation on the averaged weights: FusedAdamW.ema_weights) -----
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n, int vec) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (int64_t)gridDim.x * blockDim.x;
+  const int64_t n4 = vec ? n / 4 : 0;
+  for (int64_t k = tid; k < n4; k += nthreads) {
+    const Pack<float, 4> pa = ld_pack<float, 4>(a + k * 4), pb = ld_pack<float, 4>(b + k * 4);
+    st_pack<float, 4>(a + k * 4, pb);
+    st_pack<float, 4>(b + k * 4, pa);
+  }
+  for (int64_t e = n4 * 4 + tid; e < n; e += nthreads) {
+    const float x = a[e], y = b[e];
+    a[e] = y;
+    b[e] = x;
+  }
+}
+extern "C" int d2r_swap_f32(float* a, float* b, int64_t n, void* stream) {
+  D2R_REQUIRE(a && b && n >= 0, "d2r_swap_f32: bad arguments");
+  const uintptr_t ua = reinterpret_cast<uintptr_t>(a), ub = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)n * 4u;
+  D2R_REQUIRE(ua + bytes <= ub || ub + bytes <= ua, "d2r_swap_f32: the two ranges overlap");
+  if (n == 0) return D2R_OK;
+  const int vec = d2r_aligned16(a) && d2r_aligned16(b);
+  const int64_t work = vec ? n / 4 + 3 : n;  // (the tail of a vector launch: at most 3 elements)
+  int blocks = (int)((work + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(swap_f32_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, b, n, vec);
+  return d2r_check_launch("d2r_swap_f32");
 }
 
 // ---- overflow check of loss-scaled gradients (fp16 compute dtype): one streaming pass, flag |= any(!isfinite(g)) -----

@@ -5,6 +5,7 @@ Memory layout in HBM (one allocation each, 288 GB/GPU makes this trivially affor
     flat_g  fp32 [n_live]   gradients (``p.grad`` are views; zeroed once per step by one memset; the dW GEMMs
                             accumulate straight into it — see functional._Linear.backward)
     flat_m, flat_v fp32     AdamW moments
+    ema     fp32 [n_live]   exponential moving average of the weights (FusedAdamW(ema_decay=...) only), updated by the AdamW kernel
     flat_lp 16-bit [n_live] bf16 / fp16 shadow of the weights (16-bit compute dtypes only), rewritten by the AdamW kernel
 Live parameters are ordered by the reference's four optimiser groups (modules/train.py:287-322) so each group is
 one contiguous range = one kernel launch per group.  The 52.6 M parameters that never receive a gradient in the
@@ -12,6 +13,7 @@ reference stay outside the store and are never updated nor all-reduced (AdamW sk
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Dict, List, Optional
 
@@ -202,6 +204,12 @@ def intersect_ranges(ranges, limits=None):
     return out
 
 
+def ema_one_minus_decay(decay: float, t: int) -> float:
+    """1 - d_t of the weight EMA after optimiser step t (1-based): d_t = min(decay, (1 + t) / (10 + t)), the warm-up of
+    ``torch_ema.ExponentialMovingAverage(use_num_updates=True)``.  A double; the kernel sees it rounded once to fp32."""
+    return 1.0 - min(float(decay), (1.0 + t) / (10.0 + t))
+
+
 class FusedAdamW:
     """torch.optim.AdamW semantics (betas 0.9/0.999, eps 1e-8, decoupled weight decay) as one HIP launch per
     parameter group over the flat buffers (K14).
@@ -209,12 +217,26 @@ class FusedAdamW:
     max_grad_norm = c > 0 clips the gradient by its global L2 norm first, as ``torch.nn.utils.clip_grad_norm_(params, c)``
     before ``step()`` would (an extension beyond the reference): a streaming fp64 sum of squares over the ranges this rank
     updates (d2r_grad_sumsq), one launch that turns it into {norm, coef} on the device (d2r_grad_norm_finish), and AdamW
-    reading coef.  The pre-clip norm stays on the device (``last_grad_norm``, fp32 scalar).  None or 0: off."""
+    reading coef.  The pre-clip norm stays on the device (``last_grad_norm``, fp32 scalar).  None or 0: off.
+
+    ema_decay = D in (0, 1) keeps an exponential moving average of the live weights (an extension beyond the reference) in ``ema``,
+    fp32 [store.n] laid out like flat_w, updated by the AdamW launch itself: after step t (``step_count`` after its increment)
+    ema += (1 - d_t) * (w_new - ema) with d_t = min(D, (1 + t) / (10 + t)), as ``torch_ema.ExponentialMovingAverage`` with
+    use_num_updates=True.  ``ema_reset()`` seeds it from the weights, ``ema_weights()`` swaps it in for evaluation.  A step the fp16
+    overflow flag drops leaves ema untouched on the device; the host learns of the drop one step late (_scaler_consume), so the t
+    of the step after a dropped one is one too high - the same one-step lag the bias correction has, and no sync removes it.
+    Buffers (BatchNorm running statistics) are not averaged.  None or 0: off, and then nothing here differs from the plain step."""
 
     def __init__(self, store: ParamStore, lr: float, fc_lr: float = 5e-2, weight_decay: float = 1e-2,
-                 betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = None):
+                 betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = None,
+                 ema_decay: Optional[float] = None):
         if max_grad_norm is not None and not max_grad_norm >= 0:
             raise ValueError(f"max_grad_norm must be None or >= 0, got {max_grad_norm}")
+        if ema_decay is not None and not 0 <= ema_decay < 1:
+            raise ValueError(f"ema_decay must be None or in [0, 1), got {ema_decay}")
+        self.ema_decay = float(ema_decay) if ema_decay else None
+        self.ema = None
+        self._ema_swapped = False
         self.max_grad_norm = float(max_grad_norm) if max_grad_norm else None
         self.last_grad_norm = None
         self.store = store
@@ -242,6 +264,11 @@ class FusedAdamW:
             self._hyper_buffers()
             if self.max_grad_norm is not None:
                 self._clip_buffers(1)
+        if self.ema_decay is not None:  # eagerly too; seeded by ema_reset()
+            self.ema = torch.zeros_like(store.flat_w)
+            self._ema_omd_cpu = torch.zeros(1, dtype=torch.float32)  # pageable on purpose, see stage_hyper
+            self._ema_omd_dev = torch.zeros(1, dtype=torch.float32, device=store.flat_w.device)
+            self.ema_reset()
 
     def zero_grad(self, set_to_none: bool = False):
         self.store.zero_grad()
@@ -406,13 +433,16 @@ class FusedAdamW:
             coef = self._clip_coef(self.grad_scale / used, None, skip)
         self.step_count += 1
         st = self.store
+        omd = ema_one_minus_decay(self.ema_decay, self.step_count) if self.ema is not None else None
         for pg in self.param_groups:
             for a, b in self._owned(pg["range"]):
                 lp = None if st.flat_lp is None else st.flat_lp.data_ptr() + 2 * a
                 args = (st.flat_w.data_ptr() + 4 * a, st.flat_g.data_ptr() + 4 * a, self.m.data_ptr() + 4 * a, self.v.data_ptr() + 4 * a,
                         lp, st.lp_dtype, b - a, pg["lr"], self.betas[0], self.betas[1], self.eps, pg["weight_decay"], self.step_count,
                         self.grad_scale / used, skip)
-                if coef is None:
+                if self.ema is not None:
+                    _lib.call("d2r_adamw_step_ema", *args, coef, self.ema.data_ptr() + 4 * a, omd, _stream())
+                elif coef is None:
                     _lib.call("d2r_adamw_step", *args, _stream())
                 else:
                     _lib.call("d2r_adamw_step_clip", *args, coef, _stream())
@@ -450,6 +480,9 @@ class FusedAdamW:
         for i, pg in enumerate(self.param_groups):
             cpu[i, 0], cpu[i, 1], cpu[i, 2], cpu[i, 3] = pg["lr"], bc1, bc2s, self.grad_scale / used
         dev.copy_(cpu)  # pageable source: the runtime stages it before returning, so `cpu` may be rewritten at once
+        if self.ema is not None:  # the captured step reads 1 - d_t from its own device scalar (d_hyper keeps its layout)
+            self._ema_omd_cpu[0] = ema_one_minus_decay(self.ema_decay, self.step_count)
+            self._ema_omd_dev.copy_(self._ema_omd_cpu)
 
     def step_captured(self):
         """The launches recorded into a hipGraph (no host-side scalars).  With loss scaling on, the captured backward must have
@@ -479,10 +512,50 @@ class FusedAdamW:
             lp = None if st.flat_lp is None else st.flat_lp.data_ptr() + 2 * a
             args = (st.flat_w.data_ptr() + 4 * a, st.flat_g.data_ptr() + 4 * a, self.m.data_ptr() + 4 * a, self.v.data_ptr() + 4 * a,
                     lp, st.lp_dtype, b - a, dev.data_ptr() + 16 * i, self.betas[0], self.betas[1], self.eps, pg["weight_decay"], skip)
-            if coef is None:
+            if self.ema is not None:
+                _lib.call("d2r_adamw_step_dev_ema", *args, coef, self.ema.data_ptr() + 4 * a, self._ema_omd_dev.data_ptr(), _stream())
+            elif coef is None:
                 _lib.call("d2r_adamw_step_dev", *args, _stream())
             else:
                 _lib.call("d2r_adamw_step_dev_clip", *args, coef, _stream())
+
+    # -- weight EMA ----------------------------------------------------------------------------------------
+    def ema_reset(self):
+        """ema = the current weights (one d2r_copy_rows launch).  The trainer calls it once the starting weights are in place."""
+        if self.ema is None:
+            return
+        if self._ema_swapped:
+            raise RuntimeError("ema_reset inside ema_weights(): flat_w holds the averaged weights")
+        st = self.store
+        _lib.call("d2r_copy_rows", self.ema.data_ptr(), 4 * st.n, st.flat_w.data_ptr(), 4 * st.n, 4 * st.n, 1, _stream())
+
+    def _ema_swap(self):
+        st = self.store
+        _lib.call("d2r_swap_f32", st.flat_w.data_ptr(), self.ema.data_ptr(), st.n, _stream())
+        st.refresh_lowp()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside: the model computes with the averaged weights (flat_w and ema exchanged by one d2r_swap_f32 pass, the 16-bit shadow
+        re-derived), and a state dict taken here holds them.  On exit the live weights are back bit for bit.  Without EMA: a no-op.
+        Under the sharded optimiser a rank's ema is current for its own stripes only, so the stripes are all-gathered first (a
+        collective - every rank must enter).  Not re-entrant."""
+        if self.ema is None:
+            yield
+            return
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() is already active")
+        from .functional import wgrad_join
+        wgrad_join()
+        if self.element_ranges is not None and self.shard_gather is not None:
+            self.shard_gather(self.ema)
+        self._ema_swap()
+        self._ema_swapped = True
+        try:
+            yield
+        finally:
+            self._ema_swap()
+            self._ema_swapped = False
 
     def after_replay(self):
         """Behind a replay of a captured step: starts the copy of the overflow flag (no-op without loss scaling)."""
@@ -490,12 +563,16 @@ class FusedAdamW:
             self._scaler_after_step()
 
     def state_dict(self):
-        """Under the sharded optimiser a rank's moments are current for its own stripes only: they are all-gathered first (a
-        collective - every rank must call state_dict()), so that the result is the same complete state on every rank."""
+        """Under the sharded optimiser a rank's moments (and weight EMA) are current for its own stripes only: they are all-gathered
+        first (a collective - every rank must call state_dict()), so that the result is the same complete state on every rank."""
         if self.element_ranges is not None and self.shard_gather is not None:
             self.shard_gather(self.m)
             self.shard_gather(self.v)
+            if self.ema is not None:
+                self.shard_gather(self.ema)
         sd = dict(m=self.m, v=self.v, step=self.step_count, lrs=[pg["lr"] for pg in self.param_groups], loss_scale=self.loss_scale)
+        if self.ema is not None:
+            sd["ema"] = self.ema
         if self._scaler is not None:
             sd["scaler"] = dict(good=self._scaler["good"], skipped=self._scaler["skipped"])
         return sd
@@ -506,6 +583,11 @@ class FusedAdamW:
         self.step_count = int(sd["step"])
         for pg, lr in zip(self.param_groups, sd["lrs"]):
             pg["lr"] = lr
+        if self.ema is not None:
+            if sd.get("ema") is not None:
+                self.ema.copy_(sd["ema"])
+            else:  # a state saved without EMA: the average restarts from the weights as they are now
+                self.ema_reset()
         if self._scaler is not None and "loss_scale" in sd:  # an fp16 run resumes at the scale it had reached, not at 2^14
             self.loss_scale = float(sd["loss_scale"])
             self._scaler["used_scale"] = self.loss_scale

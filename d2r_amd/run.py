@@ -12,10 +12,12 @@ of --bert_name / --vit_name (local directories) as the reference does (run.py:12
 --only_test --load_path <best_model.pth> predicts the test split with a saved checkpoint (no training; unlabelled test entries
 allowed), --write_path writes the per-sample predictions as JSON Lines (MSDTrainer.predict); both are single-process.
 --cache_dataset device (with --data_path) decodes every split once and serves all later batches from device memory (d2r_amd.cache).
+--ema_decay D averages the weights inside the AdamW launch; the dev / test passes and best_model.pth use the average.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import logging
 import os
 import random
@@ -39,6 +41,13 @@ def _max_grad_norm(text):
     v = float(text)
     if not v >= 0:
         raise argparse.ArgumentTypeError(f"must be >= 0 (0 = no clipping), got {text}")
+    return v
+
+
+def _ema_decay(text):
+    v = float(text)
+    if not 0 <= v < 1:
+        raise argparse.ArgumentTypeError(f"must be in [0, 1) (0 = no averaging), got {text}")
     return v
 
 
@@ -95,6 +104,10 @@ def build_parser():
     p.add_argument("--num_workers", default=4, type=int)
     p.add_argument("--max_grad_norm", default=0.0, type=_max_grad_norm, help="clip the gradient to this global L2 norm before every "
                    "AdamW step, as torch.nn.utils.clip_grad_norm_ would (0 = off, the reference's behaviour)")
+    p.add_argument("--ema_decay", default=0.0, type=_ema_decay, help="keep an exponential moving average of the live weights, "
+                   "updated inside the AdamW launch; the dev / test passes run on it and best_model.pth holds it (0 = off, the "
+                   "reference's behaviour).  The decay warms up as torch_ema does with use_num_updates: step t uses "
+                   "min(ema_decay, (1 + t) / (10 + t)), always, so a short run does not keep averaging its random initialisation")
     p.add_argument("--dp_overlap", action="store_true")
     p.add_argument("--dp_grad_comm", default="f32", choices=["f32", "bf16"], help="dtype of the gradient buckets on the links")
     p.add_argument("--dp_shard_optimizer", action="store_true",
@@ -213,6 +226,9 @@ def main(argv=None):
         from .cache import cache_loaders
         cached = cache_loaders({"train": train_dl, "dev": dev_dl, "test": test_dl}, args.device, logger)
         train_dl, dev_dl, test_dl = cached["train"], cached["dev"], cached["test"]
+    if args.ema_decay and args.only_test:
+        logger.info("--ema_decay is ignored with --only_test: the checkpoint already holds the weights that were saved")
+        args.ema_decay = 0.0
     model = UnimoModelF(args=args, vision_config=vision_config, text_config=text_config, num_classes=args.num_classes)
     if args.only_test:
         trainer = MSDTrainer(test_data=test_dl, model=model, args=args, logger=logger, writer=None)
@@ -225,7 +241,8 @@ def main(argv=None):
     if trainer.samples_per_sec:
         logger.info("training throughput: %.1f samples/s on %d GPU(s)", trainer.samples_per_sec, world)
     if args.write_path is not None:  # with the weights test() ran on: the best checkpoint when the run saved one
-        trainer.predict(test_dl, args.write_path)
+        with contextlib.nullcontext() if args.load_path is not None else trainer.optimizer.ema_weights():
+            trainer.predict(test_dl, args.write_path)
 
 
 if __name__ == "__main__":

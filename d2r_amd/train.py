@@ -8,7 +8,9 @@ state-dict key names (:210-216).  Differences, all deliberate (SURVEY.md Appendi
   * the per-step host sync ``loss.item()`` (:123) is replaced by an on-device running sum read every
     ``refresh_step`` steps;
   * ``shutil.rmtree("./output")`` (:149) is opt-in (``args.cleanup_output``);
-  * optional data parallelism (args.world_size > 1 via torch.distributed, see d2r_amd.dp).
+  * optional data parallelism (args.world_size > 1 via torch.distributed, see d2r_amd.dp);
+  * optional extensions: gradient clipping (args.max_grad_norm) and a weight EMA (args.ema_decay: evaluate() / test() run on
+    the averaged weights and best_model.pth holds them; BatchNorm running statistics stay the live ones).
 """
 from __future__ import annotations
 
@@ -100,7 +102,8 @@ class MSDTrainer:
         from . import configure_runtime
         configure_runtime()
         self.optimizer = FusedAdamW(self.store, lr=self.args.lr, fc_lr=5e-2, weight_decay=1e-2,
-                                    max_grad_norm=getattr(self.args, "max_grad_norm", None) or None)
+                                    max_grad_norm=getattr(self.args, "max_grad_norm", None) or None,
+                                    ema_decay=getattr(self.args, "ema_decay", None) or None)
         if dtype == torch.float16:  # fp16 activation gradients need a scaled loss (AMP's GradScaler, here inside the optimiser)
             self.optimizer.enable_loss_scaling()
         shard = bool(getattr(self.args, "dp_shard_optimizer", False))
@@ -141,6 +144,11 @@ class MSDTrainer:
         if clip_model_dict is not None and bert_model_dict is not None:
             ingest_pretrained(self.model, clip_model_dict, bert_model_dict)
             self.store.refresh_lowp()
+        if self.optimizer.ema is not None:  # the average starts from the weights training starts from
+            self.optimizer.ema_reset()
+            self.logger.info("  Weight EMA: decay %g with warm-up min(decay, (1 + t) / (10 + t)); %d bytes of device memory "
+                             "(4 per live parameter); evaluation and best_model.pth use the averaged weights",
+                             self.optimizer.ema_decay, 4 * self.store.n)
         run_loss = torch.zeros((), dtype=torch.float32, device=self.args.device)
         clipping = self.optimizer.max_grad_norm is not None
         grad_norm = torch.zeros((), dtype=torch.float32, pin_memory=torch.cuda.is_available()) if clipping else None
@@ -227,26 +235,27 @@ class MSDTrainer:
         self.logger.info("***** Running evaluate *****")
         self.logger.info("  Num instance = %d", len(self.dev_data) * self.args.batch_size)
         self.logger.info("  Batch size = %d", self.args.batch_size)
-        result = self._eval_loop(self.dev_data, "dev")
-        result["global_step"] = epoch
-        self.logger.info("***** Dev Eval results *****")
-        for key in sorted(result.keys()):
-            self.logger.info("  %s = %s", key, str(result[key]))
-        f1, acc = result["f_score"], result["eval_accuracy"]
-        if self.writer:
-            self.writer.add_scalar(tag="dev_acc", scalar_value=acc, global_step=epoch)
-            self.writer.add_scalar(tag="dev_f1", scalar_value=f1, global_step=epoch)
-            self.writer.add_scalar(tag="dev_loss", scalar_value=result["loss"] / len(self.dev_data), global_step=epoch)
-        self.logger.info("Epoch {}/{}, best dev f1: {}, best epoch: {}, current dev f1 score: {}, acc: {}.".format(
-            epoch, self.args.num_epochs, self.best_dev_metric, self.best_dev_epoch, f1, acc))
-        if f1 >= self.best_dev_metric:
-            self.logger.info("Get better performance at epoch {}".format(epoch))
-            self.best_dev_epoch = epoch
-            self.best_dev_metric = f1
-            if self.args.save_path is not None and self.dp.rank == 0:
-                os.makedirs(self.args.save_path, exist_ok=True)
-                torch.save(self.model.state_dict(), self.args.save_path + "best_model.pth")
-                self.logger.info("Save best model at {}".format(self.args.save_path))
+        with self.optimizer.ema_weights():  # --ema_decay: the averaged weights, also in the checkpoint; a no-op without
+            result = self._eval_loop(self.dev_data, "dev")
+            result["global_step"] = epoch
+            self.logger.info("***** Dev Eval results *****")
+            for key in sorted(result.keys()):
+                self.logger.info("  %s = %s", key, str(result[key]))
+            f1, acc = result["f_score"], result["eval_accuracy"]
+            if self.writer:
+                self.writer.add_scalar(tag="dev_acc", scalar_value=acc, global_step=epoch)
+                self.writer.add_scalar(tag="dev_f1", scalar_value=f1, global_step=epoch)
+                self.writer.add_scalar(tag="dev_loss", scalar_value=result["loss"] / len(self.dev_data), global_step=epoch)
+            self.logger.info("Epoch {}/{}, best dev f1: {}, best epoch: {}, current dev f1 score: {}, acc: {}.".format(
+                epoch, self.args.num_epochs, self.best_dev_metric, self.best_dev_epoch, f1, acc))
+            if f1 >= self.best_dev_metric:
+                self.logger.info("Get better performance at epoch {}".format(epoch))
+                self.best_dev_epoch = epoch
+                self.best_dev_metric = f1
+                if self.args.save_path is not None and self.dp.rank == 0:
+                    os.makedirs(self.args.save_path, exist_ok=True)
+                    torch.save(self.model.state_dict(), self.args.save_path + "best_model.pth")
+                    self.logger.info("Save best model at {}".format(self.args.save_path))
         # unconditional: every rank reaches it whatever it decided above (a collective behind a per-rank floating-point
         # comparison could pair with the next one); nobody looks for / loads best_model.pth while rank 0 is still writing it
         self.dp.barrier()
@@ -258,9 +267,12 @@ class MSDTrainer:
         self.logger.info("\n***** Running testing *****")
         self.logger.info("  Num instance = %d", len(self.test_data) * self.args.batch_size)
         self.logger.info("  Batch size = %d", self.args.batch_size)
-        if self.args.load_path is not None:
+        if self.args.load_path is not None:  # (with --ema_decay the checkpoint holds the averaged weights already)
             self._load_checkpoint(self.args.load_path)
-        result = self._eval_loop(self.test_data, "test")
+            result = self._eval_loop(self.test_data, "test")
+        else:
+            with self.optimizer.ema_weights():
+                result = self._eval_loop(self.test_data, "test")
         result["global_step"] = epoch
         self.logger.info("***** Test Eval results *****")
         for key in sorted(result.keys()):

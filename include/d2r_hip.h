@@ -708,6 +708,22 @@ int d2r_adamw_step_clip(float* w, const float* g, float* m, float* v, void* w16 
 int d2r_adamw_step_dev_clip(float* w, const float* g, float* m, float* v, void* w16 /*or NULL*/, int w16_dtype, int64_t n,
                             const float* d_hyper, float beta1, float beta2, float eps, float weight_decay,
                             const int* d_skip /*or NULL*/, const float* d_coef, void* stream);
+/* Weight EMA (torch_ema.ExponentialMovingAverage, use_num_updates=True) in the same pass - an extension beyond the reference.
+ * The _ema forms of the two AdamW entry points above also update ema[i] += omd * (w_new[i] - ema[i]), omd = 1 - decay_t
+ * (ema_one_minus_decay in [0, 1] by value; the hipGraph form reads the device float d_ema_one_minus_decay, d_hyper keeps its
+ * layout), w_new = the fp32 weight just computed.  ema: fp32 [n], 16-byte aligned, not w; a step dropped by d_skip leaves it
+ * untouched.  d_coef is optional here (NULL: no clipping); everything else as d2r_adamw_step / d2r_adamw_step_dev. */
+int d2r_adamw_step_ema(float* w, const float* g, float* m, float* v, void* w16 /*or NULL*/, int w16_dtype, int64_t n, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                       const int* d_skip /*or NULL*/, const float* d_coef /*or NULL*/, float* ema, float ema_one_minus_decay,
+                       void* stream);
+int d2r_adamw_step_dev_ema(float* w, const float* g, float* m, float* v, void* w16 /*or NULL*/, int w16_dtype, int64_t n,
+                           const float* d_hyper, float beta1, float beta2, float eps, float weight_decay,
+                           const int* d_skip /*or NULL*/, const float* d_coef /*or NULL*/, float* ema,
+                           const float* d_ema_one_minus_decay, void* stream);
+/* a[i] <-> b[i] for i < n in one pass (16-byte vector path when both pointers are 16-byte aligned, scalar otherwise); the ranges
+ * must not overlap; n == 0 launches nothing.  Evaluation on the averaged weights swaps them in and out with this. */
+int d2r_swap_f32(float* a, float* b, int64_t n, void* stream);
 #define D2R_GRAD_NORM_PARTS 2048     /* fp64 partial sums one d2r_grad_sumsq call writes */
 #define D2R_GRAD_NORM_MAX_RANGES 16  /* element ranges one d2r_grad_sumsq call takes */
 /* slab[0..D2R_GRAD_NORM_PARTS) = fp64 partial sums of g[i]^2 over the element ranges h_ranges = host int64
