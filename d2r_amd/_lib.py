@@ -79,7 +79,7 @@ class HeadDesc(C.Structure):
                 ("lin_out", LinearParams), ("fc", LinearParams), ("x0", vp), ("x1", vp), ("labels", vp), ("js", vp),
                 ("loss", vp), ("logits", vp), ("pooled", vp), ("arena", vp), ("arena_bytes", sz), ("splitk_ws", vp),
                 ("splitk_bytes", sz), ("d_loss", vp), ("d_x0", vp), ("d_x1", vp), ("d_js", vp), ("scratch", vp),
-                ("scratch_bytes", sz), ("d_logits", vp), ("d_pooled", vp)]
+                ("scratch_bytes", sz), ("d_logits", vp), ("d_pooled", vp), ("class_weight", vp), ("label_smoothing", f32)]
 
 
 class ClipImageDesc(C.Structure):
@@ -179,7 +179,10 @@ SIGNATURES = {
     "d2r_jsdiv_bwd": (i32, [vp, vp, i32, vp, vp, vp, vp]),
     "d2r_ce_fwd": (i32, [vp, vp, i32, i32, vp, vp]),
     "d2r_ce_bwd": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+    "d2r_ce_fwd_ex": (i32, [vp, vp, vp, f32, i32, i32, vp, vp]),
+    "d2r_ce_bwd_ex": (i32, [vp, vp, vp, f32, i32, i32, vp, vp, vp]),
     "d2r_argmax_rows": (i32, [vp, i64, i64, i32, vp, vp]),
+    "d2r_confusion_add": (i32, [vp, i64, vp, i64, i32, vp, vp]),
     "d2r_block_merge_fwd": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "d2r_block_merge_bwd": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "d2r_bert_embed_fwd": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),

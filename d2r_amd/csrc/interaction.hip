@@ -959,7 +959,10 @@ extern "C" int d2r_head_fwd(const d2r_head_desc* D, void* stream) {
   TRY(lin(c, h.B, h.E, h.mm, a.z, h.mm, D->lin_out, D->pooled));
   TRY(lin(c, h.B, h.classes, h.E, D->pooled, h.E, D->fc, D->logits));
   if (!D->labels) return D2R_OK;  // prediction: logits and pooled only
-  TRY(d2r_ce_fwd(D->logits, D->labels, h.B, h.classes, a.ce, stream));
+  if (D->class_weight || D->label_smoothing != 0.f)
+    TRY(d2r_ce_fwd_ex(D->logits, D->labels, D->class_weight, D->label_smoothing, h.B, h.classes, a.ce, stream));
+  else
+    TRY(d2r_ce_fwd(D->logits, D->labels, h.B, h.classes, a.ce, stream));
   const float* xs[2] = {a.ce, D->js};
   const float coef[2] = {1.f, 1.f};
   return d2r_lincomb(xs, coef, 2, D->loss, stream);
@@ -981,7 +984,10 @@ extern "C" int d2r_head_bwd(const d2r_head_desc* D, void* stream) {
   head_plan(A, h, a);
   head_plan_bwd(Z, h, g);
   TRY(d2r_axpby(D2R_F32, 1.f, D->d_loss, 0.f, D->d_js, 1, stream));  // loss = ce + js
-  TRY(d2r_ce_bwd(D->logits, D->labels, h.B, h.classes, D->d_loss, g.dlogits, stream));
+  if (D->class_weight || D->label_smoothing != 0.f)
+    TRY(d2r_ce_bwd_ex(D->logits, D->labels, D->class_weight, D->label_smoothing, h.B, h.classes, D->d_loss, g.dlogits, stream));
+  else
+    TRY(d2r_ce_bwd(D->logits, D->labels, h.B, h.classes, D->d_loss, g.dlogits, stream));
   if (D->d_logits) TRY(d2r_axpby(D2R_F32, 1.f, D->d_logits, 1.f, g.dlogits, (int64_t)h.B * h.classes, stream));  // a second consumer of the logits
   TRY(dxg(c, h.B, h.E, h.classes, g.dlogits, h.classes, D->fc.w, g.dpooled, h.E));
   TRY(dwg(c, h.B, h.classes, h.E, g.dlogits, h.classes, D->pooled, h.E, D->fc));

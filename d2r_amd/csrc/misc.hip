@@ -404,26 +404,114 @@ extern "C" int d2r_ce_bwd(const float* logits, const int64_t* labels, int B, int
   return d2r_check_launch("d2r_ce_bwd");
 }
 
+// Class-weighted, label-smoothed cross entropy (torch.nn.functional.cross_entropy(weight=w, label_smoothing=e, reduction="mean")):
+//   row_b = (1-e) w[y_b] (-lp[b,y_b]) + (e/C) sum_c w[c] (-lp[b,c]),   loss = sum_b row_b / sum_b w[y_b]      (w == 1 when NULL)
+// The same launch shapes and per-row max / sum-of-exponentials as the plain kernels above.
+__global__ __launch_bounds__(256) void ce_fwd_ex_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                        const float* __restrict__ cw, float eps, int B, int C,
+                                                        float* __restrict__ loss) {
+  __shared__ float sh[16];
+  const float e_c = eps / (float)C;
+  float acc = 0.f, wacc = 0.f;
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const float* x = logits + (int64_t)b * C;
+    float m = -INFINITY;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, x[c]);
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s += expf(x[c] - m);
+    const float lse = m + logf(s);
+    const int64_t y = labels[b];
+    const float wy = cw ? cw[y] : 1.f;
+    float sm = 0.f;  // sum_c w[c] (-lp[b,c])
+    for (int c = 0; c < C; ++c) sm += (cw ? cw[c] : 1.f) * (lse - x[c]);
+    acc += (1.f - eps) * wy * (lse - x[y]) + e_c * sm;
+    wacc += wy;
+  }
+  const float t = block_sum(acc, sh);
+  const float wsum = cw ? block_sum(wacc, sh) : (float)B;
+  if (threadIdx.x == 0) loss[0] = t / wsum;
+}
+// dlogits[b,c] = dloss / sum_b w[y_b] * ( p[b,c] ((1-e) w[y_b] + (e/C) sum_k w[k]) - (1-e) w[y_b] [c == y_b] - (e/C) w[c] )
+// The normaliser is summed again by every workgroup (B is a few hundred at most), in a fixed order.
+__global__ __launch_bounds__(256) void ce_bwd_ex_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                        const float* __restrict__ cw, float eps, int B, int C,
+                                                        const float* __restrict__ dloss, float* __restrict__ dlogits) {
+  __shared__ float sh[16];
+  float wsum = (float)B, wall = (float)C;  // sum_b w[y_b], sum_k w[k]
+  if (cw) {
+    float wacc = 0.f;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) wacc += cw[labels[b]];
+    wsum = block_sum(wacc, sh);
+    wall = 0.f;
+    for (int c = 0; c < C; ++c) wall += cw[c];
+  }
+  const float sc = dloss[0] / wsum;
+  const float e_c = eps / (float)C;
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
+    const float* x = logits + (int64_t)b * C;
+    float m = -INFINITY;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, x[c]);
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s += expf(x[c] - m);
+    const float inv = 1.f / s;
+    const int64_t y = labels[b];
+    const float hard = (1.f - eps) * (cw ? cw[y] : 1.f);
+    const float mass = hard + e_c * wall;
+    for (int c = 0; c < C; ++c)
+      dlogits[(int64_t)b * C + c] = sc * (expf(x[c] - m) * inv * mass - (c == y ? hard : 0.f) - e_c * (cw ? cw[c] : 1.f));
+  }
+}
+extern "C" int d2r_ce_fwd_ex(const float* logits, const int64_t* labels, const float* class_weight, float label_smoothing, int B,
+                             int C, float* loss, void* stream) {
+  D2R_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "d2r_ce_fwd_ex: label_smoothing %g is outside [0, 1)", (double)label_smoothing);
+  if (!class_weight && label_smoothing == 0.f) return d2r_ce_fwd(logits, labels, B, C, loss, stream);  // the plain kernel, bit for bit
+  D2R_REQUIRE(logits && labels && loss && B >= 1 && C >= 1, "d2r_ce_fwd_ex: bad arguments");
+  hipLaunchKernelGGL(ce_fwd_ex_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, class_weight, label_smoothing, B, C,
+                     loss);
+  return d2r_check_launch("d2r_ce_fwd_ex");
+}
+extern "C" int d2r_ce_bwd_ex(const float* logits, const int64_t* labels, const float* class_weight, float label_smoothing, int B,
+                             int C, const float* dloss, float* dlogits, void* stream) {
+  D2R_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "d2r_ce_bwd_ex: label_smoothing %g is outside [0, 1)", (double)label_smoothing);
+  if (!class_weight && label_smoothing == 0.f) return d2r_ce_bwd(logits, labels, B, C, dloss, dlogits, stream);
+  D2R_REQUIRE(logits && labels && dloss && dlogits && B >= 1 && C >= 1, "d2r_ce_bwd_ex: bad arguments");
+  hipLaunchKernelGGL(ce_bwd_ex_kernel, dim3(d2r_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, labels, class_weight,
+                     label_smoothing, B, C, dloss, dlogits);
+  return d2r_check_launch("d2r_ce_bwd_ex");
+}
+
 // =====================================================================================================
 // argmax over the last dim (logits.argmax(-1) at modules/train.py:181,243): thread per row, torch.argmax's rules
 // =====================================================================================================
+// torch.argmax's rules on one row: a tie keeps the lower index, a NaN is the maximum and the first one wins
+__device__ __forceinline__ int argmax_row(const float* __restrict__ x, int cols) {
+  float best = x[0];
+  int bi = 0;
+  if (!__builtin_isnan(best)) {
+    for (int c = 1; c < cols; ++c) {
+      const float v = x[c];
+      if (__builtin_isnan(v)) {  // a NaN is the maximum; the first one wins
+        bi = c;
+        break;
+      }
+      if (v > best) best = v, bi = c;  // strict: a tie keeps the lower index
+    }
+  }
+  return bi;
+}
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ X, int64_t ld, int64_t rows, int cols,
                                                           int64_t* __restrict__ idx) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x)
+    idx[r] = argmax_row(X + r * ld, cols);
+}
+// counts[label, prediction] += 1 per labelled row: thread per row, one 64-bit integer atomic each (an evaluation batch is a few
+// dozen rows, so contention on the C x C cells does not matter; integer adds commute, the result is independent of their order)
+__global__ __launch_bounds__(256) void confusion_add_kernel(const float* __restrict__ X, int64_t ld, const int64_t* __restrict__ labels,
+                                                            int64_t rows, int C, unsigned long long* __restrict__ counts) {
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
-    const float* x = X + r * ld;
-    float best = x[0];
-    int bi = 0;
-    if (!__builtin_isnan(best)) {
-      for (int c = 1; c < cols; ++c) {
-        const float v = x[c];
-        if (__builtin_isnan(v)) {  // a NaN is the maximum; the first one wins
-          bi = c;
-          break;
-        }
-        if (v > best) best = v, bi = c;  // strict: a tie keeps the lower index
-      }
-    }
-    idx[r] = bi;
+    const int64_t y = labels[r];
+    if (y < 0 || y >= C) continue;  // unlabelled (-1) or out of range: counted nowhere
+    atomicAdd(counts + y * C + argmax_row(X + r * ld, C), 1ull);
   }
 }
 extern "C" int d2r_argmax_rows(const float* X, int64_t ld, int64_t rows, int cols, int64_t* idx, void* stream) {
@@ -435,6 +523,15 @@ extern "C" int d2r_argmax_rows(const float* X, int64_t ld, int64_t rows, int col
   hipLaunchKernelGGL(argmax_rows_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, X, ld,
                      rows, cols, idx);
   return d2r_check_launch("d2r_argmax_rows");
+}
+extern "C" int d2r_confusion_add(const float* logits, int64_t ld, const int64_t* labels, int64_t rows, int C, int64_t* counts,
+                                 void* stream) {
+  D2R_REQUIRE(rows >= 1 && C >= 1 && ld >= C, "d2r_confusion_add: bad shape (rows %lld, C %d, ld %lld)", (long long)rows, C, (long long)ld);
+  D2R_REQUIRE(logits && labels && counts, "d2r_confusion_add: null pointer");
+  const int64_t blocks = (rows + 255) / 256;
+  hipLaunchKernelGGL(confusion_add_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, logits,
+                     ld, labels, rows, C, (unsigned long long*)counts);
+  return d2r_check_launch("d2r_confusion_add");
 }
 
 // =====================================================================================================

@@ -99,7 +99,12 @@ class SyntheticMSDDataset(Dataset):
     def __len__(self):
         return self.n
 
-    def __getitem__(self, idx):
+    @property
+    def labels(self):
+        """Every sample's label, in index order (the draws of __getitem__ up to the label, without the image)."""
+        return [self._text_and_label(idx)[4] for idx in range(self.n)]
+
+    def _text_and_label(self, idx):
         g = torch.Generator().manual_seed(self.seed * 1_000_003 + idx)
         L = self.max_seq
         length = int(torch.randint(max(L // 4, 3), L + 1, (1,), generator=g))
@@ -110,6 +115,10 @@ class SyntheticMSDDataset(Dataset):
         mask[:length] = 1
         seg = torch.zeros(L, dtype=torch.long)
         label = int(torch.randint(0, self.num_classes, (1,), generator=g))
+        return ids, mask, seg, g, label
+
+    def __getitem__(self, idx):
+        ids, mask, seg, g, label = self._text_and_label(idx)
         image = torch.randn(3, self.image_size, self.image_size, generator=g)
         if self.learnable:
             image = image + 0.5 * (label - (self.num_classes - 1) / 2.0)

@@ -1206,9 +1206,22 @@ class HeadBundle:
         self.key = (w0.data_ptr(), w0._d2r_grad.data_ptr())
 
 
-def _head_fwd(x0, x1, js, labels, bundle: HeadBundle):
+def _loss_options(weight, label_smoothing, classes, device, what):
+    """(fp32 [classes] device tensor or None, float in [0, 1)) - the two options of the cross entropy, checked on the host."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise _lib.D2RError(f"{what}: label_smoothing must be in [0, 1), got {label_smoothing}")
+    if weight is not None:
+        if weight.dtype != torch.float32 or weight.dim() != 1 or weight.shape[0] != classes or weight.device != device:
+            raise _lib.D2RError(f"{what}: weight must be an fp32 [{classes}] tensor on {device}")
+        weight = weight.contiguous()
+    return weight, eps
+
+
+def _head_fwd(x0, x1, js, labels, bundle: HeadBundle, weight=None, label_smoothing=0.0):
     """One d2r_head_fwd call on contiguous fp32 inputs: -> (loss, logits, pooled, descriptor, arena).  labels=None: the label-free
-    forward (labels, js and loss NULL; loss returned as None) - the same descriptor and launches up to the logits otherwise."""
+    forward (labels, js and loss NULL; loss returned as None) - the same descriptor and launches up to the logits otherwise.
+    weight / label_smoothing: the descriptor's class_weight / label_smoothing (the caller keeps `weight` alive)."""
     B = x0.shape[0]
     lib = _lib.load()
     d = _lib.HeadDesc()
@@ -1223,6 +1236,7 @@ def _head_fwd(x0, x1, js, labels, bundle: HeadBundle):
     d.x0, d.x1, d.labels, d.js = x0.data_ptr(), x1.data_ptr(), _ptr(labels), None if labels is None else _ptr(js)
     d.loss, d.logits, d.pooled = _ptr(loss), logits.data_ptr(), pooled.data_ptr()
     d.arena, d.arena_bytes, d.splitk_ws, d.splitk_bytes = arena.data_ptr(), arena.numel(), ws.data_ptr(), ws.numel()
+    d.class_weight, d.label_smoothing = _ptr(weight), label_smoothing
     _lib.call("d2r_head_fwd", C.byref(d), _stream(), meta=dict(group="head_fwd"))
     return loss, logits, pooled, d, arena
 
@@ -1232,12 +1246,12 @@ class _Head(torch.autograd.Function):
     gradient (the end of the training graph); a gradient arriving at logits / pooled is refused."""
 
     @staticmethod
-    def forward(ctx, x0, x1, js, labels, anchor, bundle):
+    def forward(ctx, x0, x1, js, labels, anchor, bundle, weight, label_smoothing):
         x0, x1, js = x0.contiguous(), x1.contiguous(), js.contiguous()
         labels = labels.contiguous().long()
-        loss, logits, pooled, d, arena = _head_fwd(x0, x1, js, labels, bundle)
+        loss, logits, pooled, d, arena = _head_fwd(x0, x1, js, labels, bundle, weight, label_smoothing)
         ctx.save_for_backward(x0, x1, labels, logits, pooled)
-        ctx.d, ctx.keep, ctx.bundle = d, arena, bundle
+        ctx.d, ctx.keep, ctx.bundle, ctx.weight = d, arena, bundle, weight  # (the descriptor holds the weights' address)
         ctx.set_materialize_grads(False)
         return loss, logits, pooled
 
@@ -1249,7 +1263,7 @@ class _Head(torch.autograd.Function):
         d_x0, d_x1 = torch.empty_like(x0), torch.empty_like(x1)
         d_js = torch.empty((), dtype=torch.float32, device=x0.device)
         if g_loss is None and g_logits is None and g_pooled is None:
-            return d_x0.zero_(), d_x1.zero_(), d_js.zero_(), None, None, None
+            return d_x0.zero_(), d_x1.zero_(), d_js.zero_(), None, None, None, None, None
         # gradients arriving at the logits / Block's output (a second loss on them) are added to the cross-entropy path inside the call
         g_loss = torch.zeros((), dtype=torch.float32, device=x0.device) if g_loss is None else g_loss.contiguous().float()
         g_logits = None if g_logits is None else g_logits.contiguous().float()
@@ -1267,18 +1281,20 @@ class _Head(torch.autograd.Function):
             cb = getattr(p, "_d2r_ready_cb", None)
             if cb is not None:
                 cb(p)
-        return d_x0, d_x1, d_js, None, None, None
+        return d_x0, d_x1, d_js, None, None, None, None, None
 
 
-def head(x0, x1, js, labels, bundle: HeadBundle):
+def head(x0, x1, js, labels, bundle: HeadBundle, weight=None, label_smoothing=0.0):
     """Block fusion + fc + cross entropy + (ce + js) as a single autograd node: -> (loss, logits [B, classes], pooled [B, 768]).
-    labels=None: prediction, -> (None, logits, pooled) from the same launches minus the loss; only outside autograd recording."""
+    labels=None: prediction, -> (None, logits, pooled) from the same launches minus the loss; only outside autograd recording.
+    weight (fp32 [classes] on the device) / label_smoothing: the options of torch's CrossEntropyLoss, inside the same call."""
+    weight, label_smoothing = _loss_options(weight, label_smoothing, bundle.classes, x0.device, "head")
     if labels is None:
         if torch.is_grad_enabled() and any(t.requires_grad for t in (x0, x1, *bundle.params)):
             raise _lib.D2RError("head: a label-free call has no loss to differentiate; call it under torch.no_grad()")
         _, logits, pooled, _, _ = _head_fwd(x0.contiguous(), x1.contiguous(), None, None, bundle)
         return None, logits, pooled
-    return _Head.apply(x0, x1, js, labels, bundle.params[0], bundle)
+    return _Head.apply(x0, x1, js, labels, bundle.params[0], bundle, weight, label_smoothing)
 
 
 def interaction(own, other, bundle: InteractionBundle, train: bool):
@@ -1392,6 +1408,25 @@ def argmax_rows(x):
     idx = torch.empty(rows, dtype=torch.int64, device=x.device)
     _lib.call("d2r_argmax_rows", x.data_ptr(), ld, rows, cols, idx.data_ptr(), _stream())
     return idx
+
+
+def confusion_add(logits, labels, counts):
+    """counts[label, argmax(logits)] += 1 for every row whose label lies in [0, C) (d2r_confusion_add; argmax_rows' rules): logits
+    fp32 [rows, C] with unit-stride rows, labels int64 [rows], counts int64 [C, C] contiguous on the same device, updated in place
+    and returned.  Nothing is copied to the host; the call repeats over the batches of a pass."""
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise _lib.D2RError("confusion_add: fp32 [rows, classes] logits expected")
+    rows, cols = logits.shape
+    ld = logits.stride(0) if rows > 1 else cols
+    if cols > 1 and logits.stride(1) != 1 or ld < cols:
+        raise _lib.D2RError(f"confusion_add: rows must be unit-stride and not overlap (strides {tuple(logits.stride())}, shape {tuple(logits.shape)})")
+    if labels.dtype != torch.int64 or labels.numel() != rows or labels.device != logits.device:
+        raise _lib.D2RError("confusion_add: one int64 label per row, on the logits' device, expected")
+    if counts.dtype != torch.int64 or tuple(counts.shape) != (cols, cols) or not counts.is_contiguous() or counts.device != logits.device:
+        raise _lib.D2RError(f"confusion_add: counts must be a contiguous int64 [{cols}, {cols}] tensor on the logits' device")
+    labels = labels.reshape(-1).contiguous()
+    _lib.call("d2r_confusion_add", logits.data_ptr(), ld, labels.data_ptr(), rows, cols, counts.data_ptr(), _stream())
+    return counts
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1775,9 +1810,40 @@ class _CrossEntropy(torch.autograd.Function):
         return d, None
 
 
-def cross_entropy(logits, labels):
+class _CrossEntropyEx(torch.autograd.Function):
+    """Class weights and / or label smoothing: d2r_ce_fwd_ex / d2r_ce_bwd_ex."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, eps):
+        logits = logits.contiguous()
+        labels = labels.contiguous().long()
+        B, Cn = logits.shape
+        out = torch.empty((), dtype=torch.float32, device=logits.device)
+        _lib.call("d2r_ce_fwd_ex", logits.data_ptr(), labels.data_ptr(), _ptr(weight), eps, B, Cn, out.data_ptr(), _stream())
+        ctx.save_for_backward(logits, labels)
+        ctx.weight, ctx.eps = weight, eps
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        _ensure_backward_join()
+        logits, labels = ctx.saved_tensors
+        g = g.contiguous()
+        B, Cn = logits.shape
+        d = torch.empty_like(logits)
+        _lib.call("d2r_ce_bwd_ex", logits.data_ptr(), labels.data_ptr(), _ptr(ctx.weight), ctx.eps, B, Cn, g.data_ptr(), d.data_ptr(),
+                  _stream())
+        return d, None, None, None
+
+
+def cross_entropy(logits, labels, weight=None, label_smoothing=0.0):
+    """Mean cross entropy of fp32 [B, C] logits; weight (fp32 [C] on the device) and label_smoothing as in
+    torch.nn.functional.cross_entropy.  Without either option: d2r_ce_fwd / d2r_ce_bwd, as before."""
     assert logits.dtype == torch.float32
-    return _CrossEntropy.apply(logits, labels)
+    weight, eps = _loss_options(weight, label_smoothing, logits.shape[-1], logits.device, "cross_entropy")
+    if weight is None and eps == 0.0:
+        return _CrossEntropy.apply(logits, labels)
+    return _CrossEntropyEx.apply(logits, labels, weight, eps)
 
 
 class _BlockMerge(torch.autograd.Function):

@@ -881,8 +881,8 @@ class UnimoModel(D2RModule):
 
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, pixel_values=None, head=None):
         """-> (pooler_output [B,768], js_loss, aux) — models/modeling_unimo.py:786-894.
-        head = (fc Linear, labels): UnimoModelF's classifier and loss are computed here, together with Block, as one C call
-        (aux["loss"], aux["logits"]) when the one-call head applies."""
+        head = (fc Linear, labels, class weights or None, label smoothing): UnimoModelF's classifier and loss are computed here,
+        together with Block, as one C call (aux["loss"], aux["logits"]) when the one-call head applies."""
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         if token_type_ids is None:
@@ -981,7 +981,7 @@ class UnimoModel(D2RModule):
         if hb is not None:
             # the one stretch of a step where both branch streams wait for the launching stream: ~35 short launches of the
             # head's forward and backward, paced by the host when issued op by op -> one call each way
-            aux["loss"], aux["logits"], pooled = F.head(tp, vp_, js_loss, head[1], hb)
+            aux["loss"], aux["logits"], pooled = F.head(tp, vp_, js_loss, head[1], hb, *head[2:])
         else:
             pooled = self.block_fusion([tp, vp_])
         return pooled, js_loss, aux
@@ -997,19 +997,39 @@ class UnimoModelF(D2RModule):
         self.model = UnimoModel(args, vision_config, text_config)
         self.fc = Linear(text_config.hidden_size, num_classes)
         self.last_aux = None
+        # The two options of the reference's CrossEntropyLoss (models/unimo_model.py:147), in train and eval mode alike.  The weights
+        # are a plain attribute, not a buffer: best_model.pth keeps the reference's key set, and no collective touches them.
+        self.label_smoothing = float(getattr(args, "label_smoothing", 0.0) or 0.0)
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {self.label_smoothing}")
+        cw = getattr(args, "class_weights", None)
+        self.class_weight = None
+        if cw is not None:
+            cw = torch.as_tensor(cw, dtype=torch.float32).reshape(-1)
+            if cw.numel() != num_classes or not bool(torch.isfinite(cw).all()) or bool((cw < 0).any()) or not bool((cw > 0).any()):
+                raise ValueError(f"class_weights must be {num_classes} non-negative finite numbers, not all zero; got {cw.tolist()}")
+            self.class_weight = cw
+
+    def _class_weight_on(self, device):
+        """The class weights as an fp32 tensor on `device` (copied there once), or None."""
+        cw = self.class_weight
+        if cw is not None and cw.device != device:
+            cw = self.class_weight = cw.to(device)
+        return cw
 
     def forward(self, input_ids, attention_mask, token_type_ids, labels=None, images=None):
         if images is None:
             raise ValueError("images is None")
         if labels is None and torch.is_grad_enabled():
             raise RuntimeError("UnimoModelF: a call without labels has no loss to differentiate; predict under torch.no_grad()")
+        cw, eps = self._class_weight_on(images.device), self.label_smoothing
         pooled, js_loss, aux = self.model(input_ids=input_ids, attention_mask=attention_mask,
-                                          token_type_ids=token_type_ids, pixel_values=images, head=(self.fc, labels))
+                                          token_type_ids=token_type_ids, pixel_values=images, head=(self.fc, labels, cw, eps))
         if "loss" in aux:  # Block, fc, cross entropy and the sum were one call inside the model
             loss, logits = aux.pop("loss"), aux.pop("logits")
         else:
             logits = self.fc(pooled, fp32=True)
-            loss = None if labels is None else F.lincomb([1.0, 1.0], [F.cross_entropy(logits, labels), js_loss])
+            loss = None if labels is None else F.lincomb([1.0, 1.0], [F.cross_entropy(logits, labels, cw, eps), js_loss])
         aux["js_loss"] = js_loss
         self.last_aux = aux
         return loss, logits

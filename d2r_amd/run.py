@@ -13,6 +13,7 @@ of --bert_name / --vit_name (local directories) as the reference does (run.py:12
 allowed), --write_path writes the per-sample predictions as JSON Lines (MSDTrainer.predict); both are single-process.
 --cache_dataset device (with --data_path) decodes every split once and serves all later batches from device memory (d2r_amd.cache).
 --ema_decay D averages the weights inside the AdamW launch; the dev / test passes and best_model.pth use the average.
+--label_smoothing E / --class_weights {none | balanced | W0,W1,...} are the options of the cross entropy (inside its kernels).
 """
 from __future__ import annotations
 
@@ -49,6 +50,59 @@ def _ema_decay(text):
     if not 0 <= v < 1:
         raise argparse.ArgumentTypeError(f"must be in [0, 1) (0 = no averaging), got {text}")
     return v
+
+
+def _label_smoothing(text):
+    v = float(text)
+    if not 0 <= v < 1:
+        raise argparse.ArgumentTypeError(f"must be in [0, 1) (0 = off), got {text}")
+    return v
+
+
+def parse_class_weights(text, num_classes):
+    """--class_weights: 'none' -> None, 'balanced' -> 'balanced' (resolved from the training split), 'W0,W1,...' -> the list of
+    num_classes non-negative finite floats, not all zero.  Anything else: ValueError."""
+    if text in ("none", "balanced"):
+        return None if text == "none" else text
+    try:
+        w = [float(x) for x in text.split(",")]
+    except ValueError:
+        raise ValueError(f"--class_weights {text!r}: expected none, balanced or {num_classes} comma-separated numbers") from None
+    if len(w) != num_classes:
+        raise ValueError(f"--class_weights {text!r}: {len(w)} weights for --num_classes {num_classes}")
+    if any(not np.isfinite(x) or x < 0 for x in w):
+        raise ValueError(f"--class_weights {text!r}: every weight must be finite and >= 0")
+    if not any(x > 0 for x in w):
+        raise ValueError(f"--class_weights {text!r}: the weights are all zero (every loss would be 0 / 0)")
+    return w
+
+
+def balanced_class_weights(counts):
+    """N / (C * n_c) from the per-class sample counts of the training split (sklearn's compute_class_weight("balanced")).  A class
+    without a training sample has no such weight: ValueError naming it."""
+    counts = [int(n) for n in counts]
+    empty = [c for c, n in enumerate(counts) if n <= 0]
+    if empty:
+        raise ValueError(f"--class_weights balanced: class(es) {', '.join(map(str, empty))} have no sample in the training split "
+                         f"(counts {counts}); give explicit weights instead")
+    total, C = sum(counts), len(counts)
+    return [total / (C * n) for n in counts]
+
+
+def train_label_counts(args, train_json=None):
+    """Per-class sample counts of the WHOLE training split (every rank sees all of it, not its shard): the labels of train.json, or
+    of the synthetic training set."""
+    if train_json is not None:
+        import json
+        with open(train_json, "r", encoding="utf-8") as f:
+            labels = [int(s["emotion_label"]) for s in json.load(f)]
+    else:
+        from .data import SyntheticMSDDataset
+        labels = SyntheticMSDDataset(args.train_samples, args.max_seq, args.image_size, args.num_classes, seed=1).labels
+    bad = sorted({y for y in labels if not 0 <= y < args.num_classes})
+    if bad:
+        raise ValueError(f"training labels {bad} lie outside [0, {args.num_classes}) (--num_classes)")
+    return np.bincount(np.asarray(labels, dtype=np.int64), minlength=args.num_classes).tolist()
 
 
 def build_parser():
@@ -108,6 +162,11 @@ def build_parser():
                    "updated inside the AdamW launch; the dev / test passes run on it and best_model.pth holds it (0 = off, the "
                    "reference's behaviour).  The decay warms up as torch_ema does with use_num_updates: step t uses "
                    "min(ema_decay, (1 + t) / (10 + t)), always, so a short run does not keep averaging its random initialisation")
+    p.add_argument("--label_smoothing", default=0.0, type=_label_smoothing, help="label smoothing of the cross entropy, in [0, 1), as "
+                   "torch.nn.CrossEntropyLoss(label_smoothing=) (0 = off, the reference's behaviour); training, dev and test loss alike")
+    p.add_argument("--class_weights", default="none", type=str, help="per-class weights of the cross entropy, as "
+                   "torch.nn.CrossEntropyLoss(weight=): none (the reference's behaviour), balanced (N / (C * n_c) over the whole "
+                   "training split) or --num_classes comma-separated numbers W0,W1,...; not with --dp_exact")
     p.add_argument("--dp_overlap", action="store_true")
     p.add_argument("--dp_grad_comm", default="f32", choices=["f32", "bf16"], help="dtype of the gradient buckets on the links")
     p.add_argument("--dp_shard_optimizer", action="store_true",
@@ -165,6 +224,15 @@ def main(argv=None):
         raise SystemExit("--only_test / --write_path run in a single process: start without torch.distributed.run (WORLD_SIZE 1)")
     if args.cache_dataset != "off" and args.data_path is None:
         raise SystemExit("--cache_dataset device caches the files of --data_path: synthetic data has nothing to decode; run without it")
+    try:
+        class_weights = parse_class_weights(args.class_weights, args.num_classes)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if class_weights is not None and args.dp_exact:
+        # each rank divides by the weight sum of ITS labels (as DDP around the reference's loss would): with class weights that is
+        # not the global-batch loss --dp_exact promises
+        raise SystemExit("--dp_exact reproduces the global-batch loss, which per-rank class-weight normalisation does not: "
+                         "use --class_weights none with --dp_exact (--label_smoothing is fine)")
     from .config import TextConfig, VisionConfig
     from .data import MSDDataset, SyntheticMSDDataset, make_loader
     from .image import CLIP_MEAN, CLIP_STD, RESCALE, ClipCollate, processor_settings
@@ -229,6 +297,15 @@ def main(argv=None):
     if args.ema_decay and args.only_test:
         logger.info("--ema_decay is ignored with --only_test: the checkpoint already holds the weights that were saved")
         args.ema_decay = 0.0
+    if class_weights == "balanced":
+        try:
+            class_weights = balanced_class_weights(train_label_counts(args, None if args.data_path is None else files[0]))
+        except ValueError as e:
+            raise SystemExit(str(e))
+    args.class_weights = class_weights  # what the model reads: a list of num_classes floats, or None
+    if class_weights is not None or args.label_smoothing:
+        logger.info("cross entropy: class weights %s, label smoothing %g%s", class_weights, args.label_smoothing,
+                    " (no loss is computed with --only_test: no effect)" if args.only_test else "")
     model = UnimoModelF(args=args, vision_config=vision_config, text_config=text_config, num_classes=args.num_classes)
     if args.only_test:
         trainer = MSDTrainer(test_data=test_dl, model=model, args=args, logger=logger, writer=None)

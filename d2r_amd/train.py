@@ -10,7 +10,10 @@ state-dict key names (:210-216).  Differences, all deliberate (SURVEY.md Appendi
   * ``shutil.rmtree("./output")`` (:149) is opt-in (``args.cleanup_output``);
   * optional data parallelism (args.world_size > 1 via torch.distributed, see d2r_amd.dp);
   * optional extensions: gradient clipping (args.max_grad_norm) and a weight EMA (args.ema_decay: evaluate() / test() run on
-    the averaged weights and best_model.pth holds them; BatchNorm running statistics stay the live ones).
+    the averaged weights and best_model.pth holds them; BatchNorm running statistics stay the live ones);
+  * evaluate() / test() count a confusion matrix on the device (d2r_confusion_add) instead of copying labels and predictions to
+    the host per batch, and log per-class precision / recall / F1 / support after the four aggregates; they return the scalar
+    entries as before, the whole result (with "confusion" and "per_class") stays in last_dev_result / last_test_result.
 """
 from __future__ import annotations
 
@@ -35,6 +38,57 @@ def get_four_metrics(labels, predicted_labels, type="weighted"):
     from sklearn.metrics import accuracy_score, precision_recall_fscore_support
     precision, recall, f1, _ = precision_recall_fscore_support(labels, predicted_labels, average=type, zero_division="warn")
     return accuracy_score(labels, predicted_labels), recall, precision, f1
+
+
+def metrics_from_confusion(cm):
+    """The four numbers of get_four_metrics plus the per-class view, from a confusion matrix alone (cm[label][prediction], integer
+    counts: a nested list, numpy array or host tensor): {"eval_accuracy", "precision", "recall", "f_score", "per_class": [{"class",
+    "precision", "recall", "f1", "support"} per class], "confusion": nested list}.  float64 with sklearn's operations in sklearn's
+    order (precision_recall_fscore_support(average="weighted", zero_division -> 0): per-class tp / predicted, tp / true and
+    2 tp / (true + predicted) with 0 for an empty denominator, np.average(x, weights=support) over the classes that occur among
+    the labels or the predictions; accuracy_score: trace / total), so the aggregates are bit-identical to get_four_metrics on the
+    labels and predictions the matrix was counted from."""
+    import numpy as np
+    cm = np.asarray(cm, dtype=np.int64)
+    if cm.ndim != 2 or cm.shape[0] != cm.shape[1] or cm.shape[0] < 1 or (cm < 0).any():
+        raise ValueError(f"metrics_from_confusion: a square matrix of non-negative counts is expected, got shape {cm.shape}")
+    total = int(cm.sum())
+    if total == 0:
+        raise ValueError("metrics_from_confusion: the matrix counts no sample")
+    tp, true_sum, pred_sum = np.diag(cm), cm.sum(axis=1), cm.sum(axis=0)
+
+    def divide(num, den):  # sklearn's _prf_divide with zero_division -> 0
+        den = den.astype(np.float64)
+        empty = den == 0
+        den[empty] = 1
+        out = num.astype(np.float64) / den
+        out[empty] = 0.0
+        return out
+
+    precision, recall = divide(tp, pred_sum), divide(tp, true_sum)
+    f1 = divide((1 + 1.0) * tp.astype(np.float64), 1.0 * true_sum.astype(np.float64) + pred_sum.astype(np.float64))
+    seen = (true_sum + pred_sum) > 0  # sklearn's label set: the classes among the labels or the predictions
+    avg = lambda x: float(np.average(x[seen], weights=true_sum[seen]))
+    return {"eval_accuracy": float(np.float64(int(tp.sum())) / np.float64(total)), "precision": avg(precision), "recall": avg(recall),
+            "f_score": avg(f1),
+            "per_class": [{"class": c, "precision": float(precision[c]), "recall": float(recall[c]), "f1": float(f1[c]),
+                           "support": int(true_sum[c])} for c in range(cm.shape[0])],
+            "confusion": cm.tolist()}
+
+
+def log_per_class(logger, metrics):
+    """The confusion matrix and one line per class, after the aggregate lines of evaluate() / test() / predict() (which stay as
+    they were: one "  key = value" line per scalar)."""
+    logger.info("  confusion matrix (row: label, column: prediction): %s", metrics["confusion"])
+    for pc in metrics["per_class"]:
+        logger.info("  class %d: precision %.6f, recall %.6f, f1 %.6f, support %d", pc["class"], pc["precision"], pc["recall"],
+                    pc["f1"], pc["support"])
+
+
+def _reference_keys(result):
+    """What evaluate() / test() return: the scalar entries the reference's loops produce.  The confusion matrix and the per-class
+    view stay in MSDTrainer.last_dev_result / last_test_result (the whole dict, as logged)."""
+    return {k: v for k, v in result.items() if k not in ("confusion", "per_class")}
 
 
 def write_predictions(path, ids, labels, preds, probs, paths_text, paths_image):
@@ -89,6 +143,7 @@ class MSDTrainer:
         self.best_dev_epoch = None
         self.optimizer = None
         self.samples_per_sec = None
+        self.last_dev_result = self.last_test_result = None  # the last evaluate() / test() pass: its result with "confusion" and "per_class"
         if self.train_data is not None:
             self.train_num_steps = len(self.train_data) * args.num_epochs
         self.multiModal_before_train()
@@ -212,19 +267,23 @@ class MSDTrainer:
             shutil.rmtree("./output")  # the reference does this unconditionally (modules/train.py:149)
 
     def _eval_loop(self, data, desc):
-        true_labels, pred_labels = [], []
-        total_loss = torch.zeros((), dtype=torch.float32, device=self.args.device)
+        """One pass over `data`: the loss sum and the confusion matrix (d2r_confusion_add: argmax and counting in one launch per batch)
+        stay on the device, nothing is copied to the host per batch; one copy at the end, the metrics on the host from the exact
+        integer matrix (metrics_from_confusion)."""
+        classes = self.model.fc.weight.shape[0]
+        # [C * C counts | the fp32 loss sum in the low half of one more int64]: one allocation, one copy to the host
+        acc = torch.zeros(classes * classes + 1, dtype=torch.int64, device=self.args.device)
+        counts, total_loss = acc[:classes * classes].view(classes, classes), acc[classes * classes:].view(torch.float32)[:1]
         with torch.no_grad():
             for batch in data:
                 batch = self._to_device(batch)
                 (loss, logits), labels = self._step(batch, mode=desc)
                 F._lib.call("d2r_axpby", F.F32, 1.0, loss.data_ptr(), 1.0, total_loss.data_ptr(), 1, F._stream())
-                preds = logits.argmax(-1)
-                true_labels.extend(labels.view(-1).detach().cpu().tolist())
-                pred_labels.extend(preds.view(-1).detach().cpu().tolist())
-        acc, recall, precision, f1 = get_four_metrics(true_labels, pred_labels, type="weighted")
-        return {"eval_accuracy": acc, "precision": precision, "recall": recall, "f_score": f1,
-                "loss": float(total_loss.item())}
+                F.confusion_add(logits, labels.view(-1).long(), counts)  # (.long(): the same tensor when it is int64 already)
+        host = acc.cpu()  # the only host sync of the pass
+        result = metrics_from_confusion(host[:classes * classes].view(classes, classes).numpy())
+        result["loss"] = float(host[classes * classes:].view(torch.float32)[0])
+        return result
 
     def evaluate(self, epoch):
         # Data parallel: every rank evaluates the WHOLE dev set (the loaders of d2r_amd.run shard only the training set), on
@@ -240,7 +299,9 @@ class MSDTrainer:
             result["global_step"] = epoch
             self.logger.info("***** Dev Eval results *****")
             for key in sorted(result.keys()):
-                self.logger.info("  %s = %s", key, str(result[key]))
+                if key not in ("confusion", "per_class"):
+                    self.logger.info("  %s = %s", key, str(result[key]))
+            log_per_class(self.logger, result)
             f1, acc = result["f_score"], result["eval_accuracy"]
             if self.writer:
                 self.writer.add_scalar(tag="dev_acc", scalar_value=acc, global_step=epoch)
@@ -260,7 +321,8 @@ class MSDTrainer:
         # comparison could pair with the next one); nobody looks for / loads best_model.pth while rank 0 is still writing it
         self.dp.barrier()
         self.model.train()
-        return result
+        self.last_dev_result = result
+        return _reference_keys(result)
 
     def test(self, epoch):
         self.model.eval()
@@ -276,18 +338,22 @@ class MSDTrainer:
         result["global_step"] = epoch
         self.logger.info("***** Test Eval results *****")
         for key in sorted(result.keys()):
-            self.logger.info("  %s = %s", key, str(result[key]))
+            if key not in ("confusion", "per_class"):
+                self.logger.info("  %s = %s", key, str(result[key]))
+        log_per_class(self.logger, result)
         if self.writer:
             self.writer.add_scalar(tag="test_acc", scalar_value=result["eval_accuracy"])
             self.writer.add_scalar(tag="test_f1", scalar_value=result["f_score"])
             self.writer.add_scalar(tag="test_loss", scalar_value=result["loss"] / len(self.test_data))
         self.model.train()
-        return result
+        self.last_test_result = result
+        return _reference_keys(result)
 
     def predict(self, data, write_path=None):
         """Label-free prediction over `data` (eval mode, no_grad): logits, class probabilities (d2r_softmax_fwd), predicted class
         (d2r_argmax_rows) and the per-sample router outputs of both routing modules stay on the device across batches and are
-        copied to the host once at the end.  Metrics (test()'s four) when every sample is labelled (label >= 0); JSON Lines
+        copied to the host once at the end.  Metrics (test()'s four, "confusion" and "per_class": metrics_from_confusion on the matrix
+        of the labels and predictions held here) when every sample is labelled (label >= 0); JSON Lines
         records (write_predictions) with `write_path`.  -> dict of host tensors / lists, "metrics" (or None), "samples_per_sec"."""
         self.model.eval()
         self.logger.info("***** Running prediction *****")
@@ -321,11 +387,16 @@ class MSDTrainer:
         ids = [ds.ids[i] for i in range(n)] if in_order and hasattr(ds, "ids") else [None] * n
         metrics = None
         if n and all(y is not None for y in labels):
-            acc, recall, precision, f1 = get_four_metrics(labels, preds.tolist(), type="weighted")
-            metrics = {"eval_accuracy": acc, "precision": precision, "recall": recall, "f_score": f1}
+            classes = int(logits.shape[1])
+            if max(labels) >= classes:
+                raise ValueError(f"predict: label {max(labels)} with {classes} classes")
+            cm = torch.bincount(torch.tensor(labels) * classes + preds, minlength=classes * classes).view(classes, classes)  # host
+            metrics = metrics_from_confusion(cm.numpy())
             self.logger.info("***** Prediction results *****")
             for key in sorted(metrics.keys()):
-                self.logger.info("  %s = %s", key, str(metrics[key]))
+                if key not in ("confusion", "per_class"):
+                    self.logger.info("  %s = %s", key, str(metrics[key]))
+            log_per_class(self.logger, metrics)
         else:
             self.logger.info("***** Prediction results *****: not every sample is labelled, no metrics computed")
         self.logger.info("prediction throughput: %.1f samples/s (%d samples)", self.samples_per_sec, n)

@@ -288,10 +288,30 @@ int d2r_jsdiv_bwd(const float* p_logits, const float* q_logits, int B, const flo
 int d2r_ce_fwd(const float* logits, const int64_t* labels, int B, int C, float* loss /*[1]*/, void* stream);
 int d2r_ce_bwd(const float* logits, const int64_t* labels, int B, int C, const float* dloss /*[1]*/,
                float* dlogits, void* stream);
+/* d2r_ce_fwd_ex / d2r_ce_bwd_ex: cross entropy with per-class weights and label smoothing, exactly torch.nn.functional.cross_entropy(logits, labels, weight=w,
+ * label_smoothing=e, reduction="mean") - CrossEntropyLoss(weight=, label_smoothing=) at models/unimo_model.py:147.  With
+ * lp = log_softmax(logits) and w == 1 when class_weight is NULL (class_weight: fp32 [C] on the device):
+ *   loss         = sum_b [ (1-e) w[y_b] (-lp[b,y_b]) + (e/C) sum_c w[c] (-lp[b,c]) ] / sum_b w[y_b]
+ *   dlogits[b,c] = dloss / sum_b w[y_b] * ( p[b,c] ((1-e) w[y_b] + (e/C) sum_k w[k]) - (1-e) w[y_b] [c == y_b] - (e/C) w[c] )
+ * class_weight == NULL and label_smoothing == 0 launch the kernels of d2r_ce_fwd / d2r_ce_bwd: the result is bit-identical to theirs.
+ * label_smoothing outside [0, 1) (a NaN included) is refused before anything is launched.  Labels outside [0, C) are the caller's
+ * error, as for d2r_ce_fwd / d2r_ce_bwd (they are not checked on the device).  A batch whose labels all carry weight 0 divides by
+ * zero and gives NaN, as torch does.  The backward kernel sums w[y_b] over the batch again in every workgroup (no workspace). */
+int d2r_ce_fwd_ex(const float* logits, const int64_t* labels, const float* class_weight /* [C] or NULL */,
+                  float label_smoothing, int B, int C, float* loss /*[1]*/, void* stream);
+int d2r_ce_bwd_ex(const float* logits, const int64_t* labels, const float* class_weight, float label_smoothing,
+                  int B, int C, const float* dloss /*[1]*/, float* dlogits /*[B,C]*/, void* stream);
 /* Predicted class per row of fp32 X[rows, cols] (row stride ld >= cols): idx[r] = argmax_c X[r, c], with torch.argmax's rules -
  * a tie goes to the lowest index, a NaN counts as the maximum and the first NaN of a row wins, +-inf compare as usual.
  * Replaces logits.argmax(-1) at modules/train.py:181,243 (prediction from a checkpoint).  rows == 0 launches nothing. */
 int d2r_argmax_rows(const float* X, int64_t ld, int64_t rows, int cols, int64_t* idx /*[rows]*/, void* stream);
+/* d2r_confusion_add: the confusion matrix of a batch, ADDED to counts (int64 [C, C], row = label, column = prediction): counts[labels[r], argmax_c
+ * logits[r, c]] += 1 for every row r whose label lies in [0, C); a row with any other label (the loaders' -1 = unlabelled) is
+ * counted nowhere.  The prediction follows d2r_argmax_rows' rules (first maximal index, torch's NaN rule).  Integer atomics: the
+ * result does not depend on the order of the adds, and the call may be repeated on the same counts across the batches of a pass
+ * (the caller zeroes counts once).  logits fp32 [rows, C] with row stride ld; rows < 1, C < 1 and ld < C are refused. */
+int d2r_confusion_add(const float* logits, int64_t ld, const int64_t* labels, int64_t rows, int C,
+                      int64_t* counts /* [C,C], row = label, column = prediction, ADDED to */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K10 Block fusion core (models/XModules.py:541-549): z[b,c,s] = sum_r m0[b,c,r,s]*m1[b,c,r,s];
@@ -539,9 +559,13 @@ typedef struct {
   const float* d_loss;                  /* fp32 [1] */
   float* d_x0; float* d_x1; float* d_js;       /* [B, E], [B, E], [1]  OVERWRITTEN */
   void* scratch; size_t scratch_bytes;  /* >= d2r_head_bwd_scratch() */
-  /* backward, optional: gradients arriving at the OTHER outputs of the head (a second loss on the logits - distillation, label
-   * smoothing outside the model - or on Block's output), added to the cross-entropy path: fp32 [B, classes] / [B, E] or NULL */
+  /* backward, optional: gradients arriving at the OTHER outputs of the head (a second loss on the logits, e.g. distillation, or
+   * on Block's output), added to the cross-entropy path: fp32 [B, classes] / [B, E] or NULL.  (Label smoothing and class weights
+   * are class_weight / label_smoothing below: they change the reported loss too.) */
   const float* d_logits; const float* d_pooled;
+  /* optional, both ways: per-class weights (fp32 [classes] on the device, or NULL) and label smoothing in [0, 1) of the cross
+   * entropy (d2r_ce_fwd_ex / d2r_ce_bwd_ex).  NULL and 0: d2r_ce_fwd / d2r_ce_bwd, exactly the launches without these fields. */
+  const float* class_weight; float label_smoothing;
 } d2r_head_desc;
 size_t d2r_head_arena_bytes(int B, int E, int mm, int chunks, int rank, int classes);
 size_t d2r_head_bwd_scratch(int B, int E, int mm, int chunks, int rank, int classes);
