@@ -1,7 +1,7 @@
 """--cache_dataset device: the preprocessed dataset in device memory.
 
-The data layer has no augmentation (processor/dataset.py:64-102): a sample's token ids, its label and its CLIP pixel values are
-pure functions of the files on disk, and the pixel values are a function of the cropped uint8 image and the channel alone
+A sample's token ids, its label and its CLIP pixel values are pure functions of the files on disk
+(processor/dataset.py:64-102), and the pixel values are a function of the cropped uint8 image and the channel alone
 (d2r_amd.image).  So a split is decoded and resized once per run, whatever the format of its files, and every later batch is
 built on the device from
 
@@ -16,6 +16,9 @@ copy and yields the trainer's 6-tuple built by d2r_gather_rows / d2r_clip_cache_
 device.  It consumes torch's default generator exactly as the loader it replaces, and the prefill leaves that generator as it
 found it: the dropout seeds come from it (functional._next_dropout_seed), so a run with the cache takes the very steps of a run
 without.
+
+The cache holds the un-augmented crops.  A training loader may carry an ``Augmenter`` (d2r_amd.augment, --aug_crop_scale /
+--aug_flip): its batches' pixel values then come from d2r_clip_cache_augment, the same launch with a box and a flip per sample.
 """
 from __future__ import annotations
 
@@ -149,11 +152,16 @@ class DeviceDatasetCache:
         torch.cuda.synchronize(self.device)
         self.decode_log.end_pass(f"{self.split} split prefill")
 
-    def gather(self, h_idx: torch.Tensor, idx: torch.Tensor):
-        """The trainer's 6-tuple of the samples idx (int64 [B] on the device, h_idx its host copy), on the device."""
+    def gather(self, h_idx: torch.Tensor, idx: torch.Tensor, augmenter=None):
+        """The trainer's 6-tuple of the samples idx (int64 [B] on the device, h_idx its host copy), on the device.  With an
+        `augmenter` (d2r_amd.augment.Augmenter) the pixel values are its augmented view of the crops."""
+        if augmenter is None:
+            images = I.clip_cache_gather(self.crops, h_idx, idx, self.S, self.lut)
+        else:
+            images = augmenter.apply(self.crops, h_idx, idx, self.lut)
         batch = CachedBatch((I.gather_rows(self.input_ids, h_idx, idx), I.gather_rows(self.input_mask, h_idx, idx),
                              I.gather_rows(self.segment_ids, h_idx, idx), self.img_mask.expand(h_idx.numel(), -1),
-                             I.gather_rows(self.labels, h_idx, idx), I.clip_cache_gather(self.crops, h_idx, idx, self.S, self.lut)))
+                             I.gather_rows(self.labels, h_idx, idx), images))
         batch.cached_images = int(h_idx.numel())
         return batch
 
@@ -207,10 +215,12 @@ class CachedLoader:
 
     Generator fidelity: a DataLoader draws one int64 from its generator (the default one here) whenever it builds an iterator -
     every epoch, or once when it keeps persistent workers - and the samplers draw theirs as they are iterated.  The same draws are
-    made here, in the same order, so the state of the default generator after an epoch equals the plain loader's."""
+    made here, in the same order, so the state of the default generator after an epoch equals the plain loader's.
 
-    def __init__(self, loader, cache):
-        self.loader, self.cache = loader, cache
+    `augmenter` (training loader only): every batch's images are drawn through it, one draw per batch in batch order."""
+
+    def __init__(self, loader, cache, augmenter=None):
+        self.loader, self.cache, self.augmenter = loader, cache, augmenter
         self._persistent = bool(loader.persistent_workers and loader.num_workers > 0)
         self._started = False
 
@@ -239,12 +249,14 @@ class CachedLoader:
         for h_idx in batches:
             if pin:
                 h_idx = h_idx.pin_memory()
-            yield self.cache.gather(h_idx, h_idx.to(self.cache.device, non_blocking=True))
+            idx = h_idx.to(self.cache.device, non_blocking=True)
+            yield self.cache.gather(h_idx, idx) if self.augmenter is None else self.cache.gather(h_idx, idx, self.augmenter)
 
 
-def cache_loaders(loaders: dict, device, logger=None) -> dict:
+def cache_loaders(loaders: dict, device, logger=None, augmenters: dict = None) -> dict:
     """{split: DataLoader} -> {split: CachedLoader}: every split's cache is sized and checked against the free device memory
-    before anything is decoded, then allocated and prefilled in turn."""
+    before anything is decoded, then allocated and prefilled in turn.  augmenters: {split: Augmenter} for the splits whose batches
+    are augmented (the training split, if any)."""
     logger = logger or _logger
     needs = []
     for split, dl in loaders.items():
@@ -257,4 +269,4 @@ def cache_loaders(loaders: dict, device, logger=None) -> dict:
     caches = {split: DeviceDatasetCache.for_loader(dl, device, split, logger) for split, dl in loaders.items()}
     for split, dl in loaders.items():
         prefill(dl, caches[split], logger, split)
-    return {split: CachedLoader(dl, caches[split]) for split, dl in loaders.items()}
+    return {split: CachedLoader(dl, caches[split], (augmenters or {}).get(split)) for split, dl in loaders.items()}

@@ -10,7 +10,8 @@
 //
 // The dataset cache (d2r_amd/cache.py) keeps pass 2's uint8 value instead of the table's: d2r_clip_preprocess_u8 writes the crop,
 // planar [3, S, S], into a row of a device-resident cache, and d2r_clip_cache_gather maps rows picked by index through the table
-// into the fp32 batch.  d2r_gather_rows does the same row pick for the token tensors.
+// into the fp32 batch.  d2r_gather_rows does the same row pick for the token tensors.  d2r_clip_cache_augment is the gather with
+// a per-sample box of the crop resampled bilinearly to S x S and an optional mirror (d2r_amd/augment.py: random resized crop, flip).
 #include "common.h"
 
 #include <algorithm>
@@ -130,6 +131,72 @@ __global__ __launch_bounds__(256) void clip_cache_gather_kernel(const uint8_t* _
       const int64_t p = p0 + q;
       if (p < n) o[q] = sl[(int)(p / plane) * 256 + ((w[q >> 2] >> (8 * (q & 3))) & 255u)];
     }
+  }
+}
+
+// One axis of the bilinear resampling of a box of n source pixels to S output pixels (torch's interpolate, align_corners=False):
+// output position o (already mirrored when flipped) reads the taps lo and hi of the box with weight f on hi.  Integers up to
+// the one division into f, so that n == S gives lo == o and f == 0 exactly.
+struct aug_tap {
+  int lo, hi;
+  float f;
+};
+__device__ __forceinline__ aug_tap aug_axis(int o, int n, int S) {
+  const int num = (2 * o + 1) * n - S;  // < 2 * 4096 * 4096
+  const unsigned nx = num < 0 ? 0u : (unsigned)num, den = 2u * (unsigned)S;
+  const unsigned q = nx / den;
+  aug_tap t;
+  t.lo = (int)q;
+  t.hi = min(t.lo + 1, n - 1);  // clamped to the box, not to the image
+  t.f = (float)(nx - q * den) / (float)den;
+  return t;
+}
+
+// fp32, every product and sum rounded on its own (no contraction into fma): (1 - fy) * ((1 - fx) * a + fx * b) + fy * ((1 - fx) * c
+// + fx * d).  With fx == fy == 0 this is a, bit for bit, for finite table entries.
+__device__ __forceinline__ float aug_blend(float a, float b, float c, float d, float fx, float fy) {
+#pragma clang fp contract(off)
+  const float gx = 1.0f - fx, gy = 1.0f - fy;
+  const float top = gx * a + fx * b;
+  const float bot = gx * c + fx * d;
+  return gy * top + fy * bot;
+}
+
+// out[b, c, i, j] = the box aug[b] of lut[c][cache[idx[b]][c]] resampled bilinearly to S x S, mirrored when aug[b].flip: four
+// consecutive columns of one output row per thread (quads = ceil(S / 4) per row), one float4 (compiled to a 12-byte and a 4-byte
+// store) when S is a multiple of 4 and `out` 16-byte aligned, single stores otherwise.  The sixteen byte taps lie in two source rows.
+__global__ __launch_bounds__(256) void clip_cache_augment_kernel(const uint8_t* __restrict__ cache, int64_t row_bytes,
+                                                                 const int64_t* __restrict__ idx,
+                                                                 const d2r_clip_augment_desc* __restrict__ aug, int S, int quads,
+                                                                 const float* __restrict__ lut, float* __restrict__ out) {
+  __shared__ float sl[3 * 256];
+  for (int i = threadIdx.x; i < 3 * 256; i += 256) sl[i] = lut[i];
+  __syncthreads();
+  const d2r_clip_augment_desc d = aug[blockIdx.y];  // uniform: scalar loads
+  const int t = blockIdx.x * 256 + threadIdx.x;     // < 3 * 4096 * 1024
+  if (t >= 3 * S * quads) return;
+  const int line = t / quads, j0 = (t - line * quads) * 4;
+  const int c = line / S, i = line - c * S;
+  const int plane = S * S;
+  const aug_tap ty = aug_axis(i, d.h, S);
+  const uint8_t* p = cache + idx[blockIdx.y] * row_bytes + (int64_t)c * plane + d.x0;
+  const uint8_t* r0 = p + (d.y0 + ty.lo) * S;
+  const uint8_t* r1 = p + (d.y0 + ty.hi) * S;
+  const float* tab = sl + c * 256;
+  float v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int j = min(j0 + k, S - 1);  // columns past the row (S no multiple of 4) are computed again, not written
+    const aug_tap tx = aug_axis(d.flip ? S - 1 - j : j, d.w, S);
+    v[k] = aug_blend(tab[r0[tx.lo]], tab[r0[tx.hi]], tab[r1[tx.lo]], tab[r1[tx.hi]], tx.f, ty.f);
+  }
+  float* o = out + (int64_t)blockIdx.y * 3 * plane + (int64_t)line * S + j0;
+  if ((S & 3) == 0 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
+    *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (j0 + k < S) o[k] = v[k];
   }
 }
 
@@ -268,6 +335,29 @@ extern "C" int d2r_clip_cache_gather(const uint8_t* cache, int64_t cache_rows, c
   hipLaunchKernelGGL(clip_cache_gather_kernel, dim3(d2r_cdiv(row_bytes / 16, 256), B), dim3(256), 0, (hipStream_t)stream, cache, row_bytes,
                      idx, S, lut, out);
   return d2r_check_launch("d2r_clip_cache_gather");
+}
+
+extern "C" int d2r_clip_cache_augment(const uint8_t* cache, int64_t cache_rows, const int64_t* h_idx, const int64_t* idx,
+                                      const d2r_clip_augment_desc* h_aug, const d2r_clip_augment_desc* aug, int B, int S,
+                                      const float* lut, float* out, void* stream) {
+  D2R_REQUIRE(cache && h_idx && idx && h_aug && aug && lut && out, "d2r_clip_cache_augment: null pointer");
+  D2R_REQUIRE(B >= 1 && B <= 65535 && S >= 1 && S <= 4096 && cache_rows >= 1, "d2r_clip_cache_augment: bad batch %d, crop size %d or %lld cache rows",
+              B, S, (long long)cache_rows);
+  D2R_REQUIRE(d2r_aligned16(cache) && (reinterpret_cast<uintptr_t>(idx) & 7u) == 0 && (reinterpret_cast<uintptr_t>(aug) & 3u) == 0 &&
+                  (reinterpret_cast<uintptr_t>(lut) & 3u) == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0,
+              "d2r_clip_cache_augment: cache must be 16-byte, idx 8-byte, aug / lut / out 4-byte aligned");
+  if (int rc = check_rows("d2r_clip_cache_augment", "index", h_idx, B, cache_rows)) return rc;
+  for (int b = 0; b < B; ++b) {
+    const d2r_clip_augment_desc& d = h_aug[b];
+    D2R_REQUIRE(d.x0 >= 0 && d.y0 >= 0 && d.w >= 1 && d.h >= 1 && d.w <= S && d.h <= S && d.x0 <= S - d.w && d.y0 <= S - d.h,
+                "d2r_clip_cache_augment: sample %d: the %d x %d box at (%d, %d) does not lie inside the %d x %d crop", b, d.w, d.h, d.x0,
+                d.y0, S, S);
+    D2R_REQUIRE(d.flip == 0 || d.flip == 1, "d2r_clip_cache_augment: sample %d: flip is %d, not 0 or 1", b, d.flip);
+  }
+  const int quads = (S + 3) / 4;
+  hipLaunchKernelGGL(clip_cache_augment_kernel, dim3(d2r_cdiv((int64_t)3 * S * quads, 256), B), dim3(256), 0, (hipStream_t)stream, cache,
+                     (int64_t)d2r_clip_cache_row_bytes(S), idx, aug, S, quads, lut, out);
+  return d2r_check_launch("d2r_clip_cache_augment");
 }
 
 extern "C" int d2r_gather_rows(void* dst, const void* src, int64_t src_rows, int64_t row_bytes, const int64_t* h_idx, const int64_t* idx,

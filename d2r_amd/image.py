@@ -17,6 +17,8 @@ buffer of descriptors + weight tables; ``PackedImages.to_pixel_values(device)`` 
 launches the kernels on the current stream.  ``reference_preprocess`` is the same computation in numpy (tests, CPU checks).
 ``to_cache`` stops one step earlier: the uint8 crop goes into rows of a device-resident cache (``d2r_clip_preprocess_u8``), from
 which ``clip_cache_gather`` later builds the same pixel values by index (d2r_amd.cache, --cache_dataset device).
+``clip_cache_augment`` is that gather with a box per sample resized bilinearly to S x S and an optional mirror (d2r_amd.augment);
+``reference_augment`` restates it in numpy float64.
 """
 from __future__ import annotations
 
@@ -256,6 +258,66 @@ def clip_cache_gather(cache: torch.Tensor, h_idx: torch.Tensor, idx: torch.Tenso
     from .functional import _stream
     _lib.call("d2r_clip_cache_gather", cache.data_ptr(), cache.shape[0], h_idx.data_ptr(), idx.data_ptr(), B, S, lut.data_ptr(),
               out.data_ptr(), _stream())
+    return out
+
+
+AUG_FIELDS = 8  # int32 per d2r_clip_augment_desc: x0, y0, w, h, flip, three reserved zeros
+assert 4 * AUG_FIELDS == C.sizeof(_lib.ClipAugmentDesc)
+
+
+def clip_cache_augment(cache: torch.Tensor, h_idx: torch.Tensor, idx: torch.Tensor, h_aug: torch.Tensor, aug: torch.Tensor, S: int,
+                       lut: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """d2r_clip_cache_augment on the current stream: clip_cache_gather with one box per output sample, resized bilinearly to S x S
+    and mirrored when its flip is set.  aug is int32 [B, 8] on the device (x0, y0, w, h, flip, 0, 0, 0 per sample), h_aug its host
+    copy; the library checks indices and boxes on the host copies before it enqueues anything."""
+    B = h_idx.numel()
+    dev = cache.device
+    if not (cache.dtype == torch.uint8 and h_idx.dtype == torch.int64 and idx.dtype == torch.int64 and lut.dtype == torch.float32 and
+            h_aug.dtype == torch.int32 and aug.dtype == torch.int32):
+        raise TypeError("cache uint8, idx int64, aug int32, lut float32 expected")
+    if cache.dim() != 2 or cache.shape[1] != cache_row_bytes(S) or idx.numel() != B or lut.numel() != 768 or \
+            tuple(h_aug.shape) != (B, AUG_FIELDS) or tuple(aug.shape) != (B, AUG_FIELDS):
+        raise ValueError("cache / index / descriptor / lut sizes disagree")
+    if not all(t.is_cuda and t.device == dev and t.is_contiguous() for t in (cache, idx, aug, lut)) or \
+            any(t.is_cuda or not t.is_contiguous() for t in (h_idx, h_aug)):
+        raise ValueError("device tensors must be contiguous on one GPU, h_idx / h_aug on the host")
+    if out is None:
+        out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * 3 * S * S or out.device != dev:
+        raise ValueError("out must be a contiguous fp32 [B, 3, S, S] tensor on the cache's device")
+    from .functional import _stream
+    _lib.call("d2r_clip_cache_augment", cache.data_ptr(), cache.shape[0], h_idx.data_ptr(), idx.data_ptr(),
+              C.cast(h_aug.data_ptr(), C.POINTER(_lib.ClipAugmentDesc)), aug.data_ptr(), B, S, lut.data_ptr(), out.data_ptr(), _stream())
+    return out
+
+
+def reference_augment(crop: np.ndarray, box, S: int, table: np.ndarray = None) -> np.ndarray:
+    """CPU restatement of d2r_clip_cache_augment for one sample, in float64: `crop` uint8 planar [3, S, S] (a cache row), `box` =
+    (x0, y0, w, h, flip), `table` fp32 [3, 256] -> float64 [3, S, S].  The coordinates are computed in integers exactly as the kernel
+    does; only the blend is carried out in float64 instead of fp32."""
+    x0, y0, w, h, flip = (int(v) for v in box)
+    crop = np.asarray(crop)
+    if crop.dtype != np.uint8 or crop.shape != (3, S, S):
+        raise ValueError(f"expected a uint8 [3, {S}, {S}] crop, got {crop.dtype} {crop.shape}")
+    if not (x0 >= 0 and y0 >= 0 and w >= 1 and h >= 1 and x0 + w <= S and y0 + h <= S and flip in (0, 1)):
+        raise ValueError(f"box {tuple(box)} does not lie inside the {S} x {S} crop")
+    table = normalize_table() if table is None else table
+
+    def axis(o, n):
+        nx = np.maximum((2 * o + 1) * n - S, 0)
+        lo = nx // (2 * S)
+        return lo, np.minimum(lo + 1, n - 1), (nx % (2 * S)).astype(np.float64) / float(2 * S)
+
+    pos = np.arange(S, dtype=np.int64)
+    ix0, ix1, fx = axis(S - 1 - pos if flip else pos, w)
+    iy0, iy1, fy = axis(pos, h)
+    fx, fy = fx[None, :], fy[:, None]
+    out = np.empty((3, S, S), np.float64)
+    for c in range(3):
+        T = np.asarray(table[c], np.float64)[crop[c]]
+        a, b = T[np.ix_(y0 + iy0, x0 + ix0)], T[np.ix_(y0 + iy0, x0 + ix1)]
+        c_, d = T[np.ix_(y0 + iy1, x0 + ix0)], T[np.ix_(y0 + iy1, x0 + ix1)]
+        out[c] = (1 - fy) * ((1 - fx) * a + fx * b) + fy * ((1 - fx) * c_ + fx * d)
     return out
 
 

@@ -14,6 +14,7 @@ allowed), --write_path writes the per-sample predictions as JSON Lines (MSDTrain
 --cache_dataset device (with --data_path) decodes every split once and serves all later batches from device memory (d2r_amd.cache).
 --ema_decay D averages the weights inside the AdamW launch; the dev / test passes and best_model.pth use the average.
 --label_smoothing E / --class_weights {none | balanced | W0,W1,...} are the options of the cross entropy (inside its kernels).
+--aug_crop_scale LO / --aug_flip P (with --data_path) augment the training images on the device (d2r_amd.augment).
 """
 from __future__ import annotations
 
@@ -56,6 +57,20 @@ def _label_smoothing(text):
     v = float(text)
     if not 0 <= v < 1:
         raise argparse.ArgumentTypeError(f"must be in [0, 1) (0 = off), got {text}")
+    return v
+
+
+def _aug_crop_scale(text):
+    v = float(text)
+    if not 0 < v <= 1:
+        raise argparse.ArgumentTypeError(f"must be in (0, 1] (1 = no cropping), got {text}")
+    return v
+
+
+def _aug_flip(text):
+    v = float(text)
+    if not 0 <= v <= 1:
+        raise argparse.ArgumentTypeError(f"must be in [0, 1] (0 = no flipping), got {text}")
     return v
 
 
@@ -186,6 +201,11 @@ def build_parser():
     p.add_argument("--cache_dataset", default="off", choices=["off", "device"], help="with --data_path: decode and resize every "
                    "image once, keep the uint8 crops and the token tensors of every split in device memory (150,528 bytes per image "
                    "at 224 x 224) and build every batch there by index; the run takes the same steps as without it (d2r_amd.cache)")
+    p.add_argument("--aug_crop_scale", default=1.0, type=_aug_crop_scale, help="with --data_path: random resized crop of the "
+                   "training images on the device: a box of LO..1 of the image's area, aspect ratio 3/4..4/3, resized bilinearly to the "
+                   "crop size (torchvision's RandomResizedCrop); in (0, 1], 1 = off, the reference's behaviour")
+    p.add_argument("--aug_flip", default=0.0, type=_aug_flip, help="with --data_path: mirror each training image horizontally with "
+                   "this probability, in [0, 1] (0 = off, the reference's behaviour); dev and test images are never augmented")
     p.add_argument("--pretrained", action="store_true", help="model configs, weights and image preprocessing from the local "
                    "--bert_name / --vit_name checkpoints (BertModel, CLIPModel.vision_model, preprocessor_config.json)")
     return p
@@ -224,6 +244,10 @@ def main(argv=None):
         raise SystemExit("--only_test / --write_path run in a single process: start without torch.distributed.run (WORLD_SIZE 1)")
     if args.cache_dataset != "off" and args.data_path is None:
         raise SystemExit("--cache_dataset device caches the files of --data_path: synthetic data has nothing to decode; run without it")
+    augment = args.aug_crop_scale < 1.0 or args.aug_flip > 0.0
+    if augment and args.data_path is None:
+        raise SystemExit("--aug_crop_scale / --aug_flip augment the uint8 crops of the images of --data_path: synthetic images are "
+                         "not such crops; run without them")
     try:
         class_weights = parse_class_weights(args.class_weights, args.num_classes)
     except ValueError as e:
@@ -287,13 +311,23 @@ def main(argv=None):
     if not args.only_test:
         train_dl, dev_dl = loader(args.train_samples, 1, True, 0), loader(args.eval_samples, 2, False, 1)
     test_dl = loader(args.eval_samples, 3, False, 2)
+    augmenter = None
+    if augment and args.only_test:
+        logger.info("--aug_crop_scale / --aug_flip are ignored with --only_test: only training batches are augmented")
+    elif augment:
+        # a generator of its own, seeded from (--seed, rank): each rank augments its shard with its own stream, and the default
+        # generator (samplers, dropout seeds) is never drawn from
+        from .augment import Augmenter
+        augmenter = Augmenter(S, args.aug_crop_scale, args.aug_flip, seed=args.seed, rank=rank)
     if args.cache_dataset == "device" and args.only_test:
         logger.info("--cache_dataset device is ignored with --only_test: a single pass over the test split gains nothing")
     elif args.cache_dataset == "device":
         # every rank caches the whole of each split (the training shards change every epoch); the default generator is untouched
         from .cache import cache_loaders
-        cached = cache_loaders({"train": train_dl, "dev": dev_dl, "test": test_dl}, args.device, logger)
+        cached = cache_loaders({"train": train_dl, "dev": dev_dl, "test": test_dl}, args.device, logger,
+                               augmenters={"train": augmenter} if augmenter is not None else None)
         train_dl, dev_dl, test_dl = cached["train"], cached["dev"], cached["test"]
+        augmenter = None  # the cached training loader augments its own batches
     if args.ema_decay and args.only_test:
         logger.info("--ema_decay is ignored with --only_test: the checkpoint already holds the weights that were saved")
         args.ema_decay = 0.0
@@ -313,7 +347,7 @@ def main(argv=None):
         trainer.predict(test_dl, args.write_path)
         return
     trainer = MSDTrainer(train_data=train_dl, dev_data=dev_dl, test_data=test_dl, model=model, args=args, logger=logger,
-                         writer=None)
+                         writer=None, augmenter=augmenter)
     trainer.train(clip_sd, bert_sd)  # None, None without --pretrained: randomly initialised encoders
     if trainer.samples_per_sec:
         logger.info("training throughput: %.1f samples/s on %d GPU(s)", trainer.samples_per_sec, world)

@@ -11,6 +11,8 @@ state-dict key names (:210-216).  Differences, all deliberate (SURVEY.md Appendi
   * optional data parallelism (args.world_size > 1 via torch.distributed, see d2r_amd.dp);
   * optional extensions: gradient clipping (args.max_grad_norm) and a weight EMA (args.ema_decay: evaluate() / test() run on
     the averaged weights and best_model.pth holds them; BatchNorm running statistics stay the live ones);
+  * optional image augmentation of the TRAINING batches (``augmenter``, d2r_amd.augment: random resized crop and flip on the
+    device; a CachedLoader carries its own); evaluate() / test() / predict() never augment;
   * evaluate() / test() count a confusion matrix on the device (d2r_confusion_add) instead of copying labels and predictions to
     the host per batch, and log per-class precision / recall / F1 / support after the four aggregates; they return the scalar
     entries as before, the whole result (with "confusion" and "per_class") stays in last_dev_result / last_test_result.
@@ -131,8 +133,9 @@ def ingest_pretrained(model, clip_model_dict, bert_model_dict):
 
 class MSDTrainer:
     def __init__(self, train_data=None, dev_data=None, test_data=None, model=None, args=None, logger=None,
-                 writer=None) -> None:
+                 writer=None, augmenter=None) -> None:
         self.train_data, self.dev_data, self.test_data = train_data, dev_data, test_data
+        self.augmenter = augmenter  # training batches of packed images only (a CachedLoader augments its own batches)
         self.model, self.args = model, args
         self.logger = logger or logging.getLogger(__name__)
         self.writer = writer
@@ -178,11 +181,13 @@ class MSDTrainer:
         self.store.refresh_lowp()
         self.logger.info("Load model successful!")
 
-    def _to_device(self, batch):
+    def _to_device(self, batch, augmenter=None):
         # tensors are copied; a packed batch of images (MSDDataset + ClipCollate: PackedImages, or PackedJpegImages with
-        # image_decode="device") becomes its CLIP pixel values on the device
+        # image_decode="device") becomes its CLIP pixel values on the device - through `augmenter` when the training loop passes one
+        def pixel_values(t):
+            return t.to_pixel_values(self.args.device) if augmenter is None else augmenter.apply_packed(t, self.args.device)
         return tuple(t.to(self.args.device, non_blocking=True) if isinstance(t, torch.Tensor) else
-                     t.to_pixel_values(self.args.device) if hasattr(t, "to_pixel_values") else t for t in batch)
+                     pixel_values(t) if hasattr(t, "to_pixel_values") else t for t in batch)
 
     # -- training (modules/train.py:77-159) -----------------------------------------------------------
     def train(self, clip_model_dict=None, bert_model_dict=None):
@@ -204,6 +209,9 @@ class MSDTrainer:
             self.logger.info("  Weight EMA: decay %g with warm-up min(decay, (1 + t) / (10 + t)); %d bytes of device memory "
                              "(4 per live parameter); evaluation and best_model.pth use the averaged weights",
                              self.optimizer.ema_decay, 4 * self.store.n)
+        augmenter = self.augmenter or getattr(self.train_data, "augmenter", None)
+        if augmenter is not None:
+            self.logger.info("  Image augmentation of the training batches: %s", augmenter.describe())
         run_loss = torch.zeros((), dtype=torch.float32, device=self.args.device)
         clipping = self.optimizer.max_grad_norm is not None
         grad_norm = torch.zeros((), dtype=torch.float32, pin_memory=torch.cuda.is_available()) if clipping else None
@@ -221,7 +229,7 @@ class MSDTrainer:
                 self.step += 1
                 if self.step == warm + 1 and t_mark is None:
                     t_mark = time.time()
-                packed, batch = batch, self._to_device(batch)
+                packed, batch = batch, self._to_device(batch, self.augmenter)
                 self.decode_log.note(packed)
                 self.dp.begin_step()
                 (loss, logits), labels = self._step(batch, mode="train")

@@ -641,6 +641,28 @@ int d2r_clip_cache_gather(const uint8_t* cache, int64_t cache_rows, const int64_
                           const float* lut, float* out, void* stream);
 int d2r_gather_rows(void* dst, const void* src, int64_t src_rows, int64_t row_bytes, const int64_t* h_idx, const int64_t* idx, int B,
                     void* stream);
+/* K21  Image augmentation on the cache rows (d2r_amd/augment.py, --aug_crop_scale / --aug_flip).  d2r_clip_cache_augment is
+ * d2r_clip_cache_gather with a box per output sample that is cut out of the normalised crop, resized bilinearly to S x S and mirrored when flip is set - torch's
+ * interpolate(mode="bilinear", align_corners=False) on lut[c][crop][:, y0:y0+h, x0:x0+w], then .flip(-1).
+ * Per sample b (row P = cache[idx[b]], T[c][v] = lut[c*256 + v]), channel c and output pixel (i, j):
+ *   jj = flip ? S-1-j : j;  nx = max((2*jj+1)*w - S, 0) in integers;  ix0 = nx / (2*S), ix1 = min(ix0+1, w-1),
+ *   fx = float(nx % (2*S)) / float(2*S);  ny, iy0, iy1, fy likewise from i and h;
+ *   out[b,c,i,j] = (1-fy)*((1-fx)*a + fx*b_) + fy*((1-fx)*c_ + fx*d_) in fp32, every operation rounded on its own, with
+ *   a, b_, c_, d_ = T[c][P[c, y0+iy{0,1}, x0+ix{0,1}]].
+ * The upper taps are clamped to the box, not to the crop.  The box (0, 0, S, S) with flip 0 has fx = fy = 0 and ix0 = j: the call
+ * then writes the very bits d2r_clip_cache_gather writes.  out is fp32 [B, 3, S, S], OVERWRITTEN.
+ * One descriptor per output sample, 32 bytes, the reserved fields zero.  h_idx / h_aug are the host copies of idx / aug: an index
+ * outside [0, cache_rows), a box with x0 < 0, y0 < 0, w < 1, h < 1, x0 + w > S or y0 + h > S, or a flip other than 0 / 1 is refused
+ * before anything is enqueued, and a refused call writes nothing. */
+typedef struct {
+  int32_t x0, y0;      /* box origin in the crop (column, row) */
+  int32_t w, h;        /* box size: 1 <= w <= S - x0, 1 <= h <= S - y0 */
+  int32_t flip;        /* 1: mirrored horizontally after the resize */
+  int32_t reserved[3]; /* zero */
+} d2r_clip_augment_desc;
+int d2r_clip_cache_augment(const uint8_t* cache, int64_t cache_rows, const int64_t* h_idx, const int64_t* idx,
+                           const d2r_clip_augment_desc* h_aug, const d2r_clip_augment_desc* aug, int B, int S, const float* lut,
+                           float* out, void* stream);
 /* K19  Baseline JPEG decoding of a batch of images on the device (processor/dataset.py:89: Image.open(p).convert("RGB") in the
  * reference's loader workers), bit-identical to libjpeg-turbo's default path as Pillow uses it: Huffman decoding, ISLOW IDCT with
  * its range-limit table, fancy h2v1 / h2v2 chroma upsampling, fixed-point YCbCr -> RGB.  The host (d2r_amd/jpeg.py) parses the
