@@ -476,6 +476,26 @@ __global__ __launch_bounds__(512) void gemm8_fwd_kernel(const G8GroupF g) {
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // bias values of this lane's sixteen accumulator columns, fetched BEFORE the main loop from clamped addresses (older than every DMA of
+  // the loop: its counted waits are unaffected); the accumulator-to-LDS passes of the epilogue find them in registers
+  float bias_r[4][4];
+  {
+    const int lane_ = threadIdx.x & 63, wc_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 3;
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) bias_r[nj][r] = 0.f;
+    if (P.bias) {
+#pragma unroll
+      for (int nj = 0; nj < 4; ++nj)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int col = n0 + wc_ * 64 + (nj >> 1) * 32 + (nj & 1) * 16 + (lane_ >> 4) * 4 + r;
+          const float b = P.bias[min(col, N - 1)];
+          bias_r[nj][r] = col < N ? b : 0.f;
+        }
+    }
+  }
   g8_main<E, LAYOUT, false>(reinterpret_cast<const E*>(P.A), reinterpret_cast<const E*>(P.B), M, N, P.K, P.lda, P.ldb, m0, n0, smem, acc, accb, false,
                                  D2R_G8_STAMPS ? g.stamps : nullptr);
 
@@ -493,7 +513,6 @@ __global__ __launch_bounds__(512) void gemm8_fwd_kernel(const G8GroupF g) {
   const E* Rg = reinterpret_cast<const E*>(P.R);
   const E* Gg = reinterpret_cast<const E*>(P.G);
   const float alpha = P.alpha;
-  const float* bias = P.bias;
   g8_barrier();
 #pragma unroll
   for (int mh = 0; mh < 2; ++mh) {
@@ -502,15 +521,11 @@ __global__ __launch_bounds__(512) void gemm8_fwd_kernel(const G8GroupF g) {
 #pragma unroll
       for (int nj = 0; nj < 4; ++nj) {
         const int cl = (nj >> 1) * 32 + (nj & 1) * 16 + fq * 4;
-        const int col = n0 + wc * 64 + cl;
-        Pack<E, 4> pk;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float bv = (bias && col + r < N) ? bias[col + r] : 0.f;
-          pk.v[r] = (E)(alpha * acc[mh * 4 + i][nj][r] + bv);
-        }
-        st_pack<E, 4>(Cs + (i * 16 + fr) * LDE + cl, pk);
+        st_pack<E, 4>(Cs + (i * 16 + fr) * LDE + cl, epilogue_stage4<E>(alpha, acc[mh * 4 + i][nj], bias_r[nj]));
       }
+    // G, R and the old C are loaded inside the pack loop, as before: fetched as one batch per half (gemm_args.h epilogue_fetch, as the
+    // 128-wide kernels do) the launches with R or G.relu were 1 us SLOWER than with the loads in the loop - the selects among eight packs and
+    // the burst of a whole workgroup's loads cost more than the waits they replace (profiles/gemm_epilogue_fetch.log)
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
 #pragma unroll 1

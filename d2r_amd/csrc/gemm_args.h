@@ -292,11 +292,95 @@ __device__ __forceinline__ void act_grad_mul_vec(int act, const float (&r)[N], f
 static __device__ __attribute__((noinline)) float act_apply_cold(int act, float x) { return act_apply(act, x); }
 static __device__ __attribute__((noinline)) float act_grad_cold(int act, float r) { return act_grad(act, r); }
 
-// One 8-column pack of the LDS-staged 16-bit epilogue, shared by the MFMA GEMM kernels:
-//   out = act(pv) [* act'(G)] [+ R] [+ beta * C_old],  preact <- pv;   `n_ok` = valid columns of the pack (8 = whole pack)
+// alpha * acc + bias of four consecutive accumulator columns, rounded to the 16-bit type: what the LDS-DMA kernels stage in LDS for the pack
+// loop.  fp16: v_fma_mixlo / mixhi_f16, an fp32 fused multiply-add whose result goes to fp16 in the same instruction.  It is what the
+// compiler has picked for this expression in every build so far; with the bias in registers it prefers a packed fp32 fma followed by a
+// packed conversion, which does not give the same bits in every element (measured: the training step's outputs differ after 30 steps,
+// bf16 - which has no such instruction - stays bit-identical).  The instruction is therefore written out: the results of a step must
+// not depend on which form the vectoriser likes.
+template <typename E>
+__device__ __forceinline__ Pack<E, 4> epilogue_stage4(float alpha, const f32x4& acc, const float (&b)[4]) {
+  if constexpr (H16<E>::DT == D2R_F16) {
+    typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+    u32x2 w;
+    unsigned lo, hi;
+    asm("v_fma_mixlo_f16 %0, %1, %2, %3" : "=v"(lo) : "v"(alpha), "v"(acc[0]), "v"(b[0]));
+    asm("v_fma_mixhi_f16 %0, %1, %2, %3" : "+v"(lo) : "v"(alpha), "v"(acc[1]), "v"(b[1]));
+    asm("v_fma_mixlo_f16 %0, %1, %2, %3" : "=v"(hi) : "v"(alpha), "v"(acc[2]), "v"(b[2]));
+    asm("v_fma_mixhi_f16 %0, %1, %2, %3" : "+v"(hi) : "v"(alpha), "v"(acc[3]), "v"(b[3]));
+    w[0] = lo, w[1] = hi;
+    return __builtin_bit_cast(Pack<E, 4>, w);
+  } else {
+    Pack<E, 4> pk;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pk.v[r] = (E)(alpha * acc[r] + b[r]);
+    return pk;
+  }
+}
+
+// ---- operands of the 16-bit pack epilogue: fetched in ONE batch ----------------------------------------------------------------------
+// A lane of the LDS-staged epilogue leaves NP packs of 8 columns through a rolled loop (one copy of the arithmetic above).  Loading the
+// packs of G (gradient reference), R (residual) and the old C (beta != 0) inside that loop exposes one global-memory latency per
+// iteration: every wave of the workgroup is in its epilogue at the same moment, nothing covers the wait.  The kernels therefore issue
+// all NP loads of every operand that is present up front (epilogue_fetch, unrolled, followed by a sched_barrier) and the rolled loop picks
+// its pack by the wave-uniform iteration number (epilogue_pick: selects, never a run-time array index - that would go to scratch).
+// Same values, same arithmetic, same order: only the waiting changes.  The packs travel as raw 16 bytes.
+typedef __attribute__((ext_vector_type(4))) unsigned epi_raw_t;
+template <int NP>
+struct EpiOperands {
+  epi_raw_t g[NP], r[NP], c[NP];  // (an operand that is absent is never loaded and never read)
+};
+// Slot numbers are compile-time constants from the front end on (a recursion, not an unrolled loop: the batch has to be split into
+// registers before the rolled pack loop is formed around its uses - as an indexed array it ended up in scratch).
+template <int K> struct EpiSlot { static constexpr int value = K; };
+template <int K, int NP, typename F>
+__device__ __forceinline__ void epi_for_slots(F&& f) {
+  if constexpr (K < NP) {
+    f(EpiSlot<K>{});
+    epi_for_slots<K + 1, NP>(f);
+  }
+}
+// `at_c(k)` / `at_r(k)`: element offset of pack k in the layout of C / of R, CLAMPED by the caller to a whole pack inside the operand (the
+// packs of rows >= M and of columns past N - 8 are fetched from a valid address and never used): no load sits under a per-lane branch.
+template <typename H, int NP, typename AtC, typename AtR>
+__device__ __forceinline__ void epilogue_fetch(EpiOperands<NP>& ops, const H* Cold, const H* Rg, const H* Gg, AtC at_c, AtR at_r) {
+  if (Gg) epi_for_slots<0, NP>([&](auto k) { ops.g[k.value] = *reinterpret_cast<const epi_raw_t*>(Gg + at_c(k.value)); });
+  if (Rg) epi_for_slots<0, NP>([&](auto k) { ops.r[k.value] = *reinterpret_cast<const epi_raw_t*>(Rg + at_r(k.value)); });
+  if (Cold) epi_for_slots<0, NP>([&](auto k) { ops.c[k.value] = *reinterpret_cast<const epi_raw_t*>(Cold + at_c(k.value)); });
+  __builtin_amdgcn_sched_barrier(0);  // the whole batch is in flight before anything behind it is scheduled
+}
+template <typename H, int NP>
+__device__ __forceinline__ Pack<H, 8> epilogue_pick(const epi_raw_t (&p)[NP], int slot) {  // slot: wave-uniform
+  epi_raw_t r = p[0];
+  epi_for_slots<1, NP>([&](auto k) { r = slot == k.value ? p[k.value] : r; });
+  return __builtin_bit_cast(Pack<H, 8>, r);
+}
+
+// Where a whole pack's operands come from: memory, loaded where they are needed (the generic tiled kernel), or slot `slot` of a batch
+// that is already in registers (the LDS-DMA kernels).
 template <typename H>
-__device__ __forceinline__ void epilogue_pack8(const GemmArgs& g, const Pack<H, 8>& pv, H* Cg, H* Pg, const H* Rg, const H* Gg, int64_t ci,
-                                               int64_t ri, int n_ok) {
+struct EpiFromMemory {
+  const H *Cg, *Rg, *Gg;
+  int64_t ci, ri;
+  __device__ __forceinline__ Pack<H, 8> g() const { return ld_pack<H, 8>(Gg + ci); }
+  __device__ __forceinline__ Pack<H, 8> r() const { return ld_pack<H, 8>(Rg + ri); }
+  __device__ __forceinline__ Pack<H, 8> c() const { return ld_pack<H, 8>(Cg + ci); }
+};
+template <typename H, int NP>
+struct EpiFromBatch {
+  const EpiOperands<NP>& ops;
+  int slot;
+  __device__ __forceinline__ Pack<H, 8> g() const { return epilogue_pick<H, NP>(ops.g, slot); }
+  __device__ __forceinline__ Pack<H, 8> r() const { return epilogue_pick<H, NP>(ops.r, slot); }
+  __device__ __forceinline__ Pack<H, 8> c() const { return epilogue_pick<H, NP>(ops.c, slot); }
+};
+
+// One 8-column pack of the LDS-staged 16-bit epilogue, shared by the MFMA GEMM kernels (compute / store part):
+//   out = act(pv) [* act'(G)] [+ R] [+ beta * C_old],  preact <- pv;   `n_ok` = valid columns of the pack (8 = whole pack);
+// `src` hands over the operand packs of a whole pack; the ragged right edge reads its elements from memory
+template <typename H, typename Src>
+__device__ __forceinline__ void epilogue_pack8_apply(const GemmArgs& g, const Pack<H, 8>& pv, const Src& src, H* Cg, H* Pg, const H* Rg,
+                                                     const H* Gg, int64_t ci, int64_t ri, int n_ok) {
   float v[8], t[8];
 #pragma unroll
   for (int u = 0; u < 8; ++u) v[u] = (float)pv.v[u];
@@ -304,18 +388,18 @@ __device__ __forceinline__ void epilogue_pack8(const GemmArgs& g, const Pack<H, 
     if (Pg) st_pack<H, 8>(Pg + ci, pv);
     act_apply_vec<8>(g.act, v);
     if (Gg) {
-      const Pack<H, 8> gv = ld_pack<H, 8>(Gg + ci);
+      const Pack<H, 8> gv = src.g();
 #pragma unroll
       for (int u = 0; u < 8; ++u) t[u] = (float)gv.v[u];
       act_grad_mul_vec<8>(g.gact, t, v);
     }
     if (Rg) {
-      const Pack<H, 8> rv = ld_pack<H, 8>(Rg + ri);
+      const Pack<H, 8> rv = src.r();
 #pragma unroll
       for (int u = 0; u < 8; ++u) v[u] += (float)rv.v[u];
     }
     if (g.beta != 0.f) {
-      const Pack<H, 8> cv = ld_pack<H, 8>(Cg + ci);
+      const Pack<H, 8> cv = src.c();
 #pragma unroll
       for (int u = 0; u < 8; ++u) v[u] += g.beta * (float)cv.v[u];
     }
@@ -338,4 +422,16 @@ __device__ __forceinline__ void epilogue_pack8(const GemmArgs& g, const Pack<H, 
       Cg[ci + u] = (H)x;
     }
   }
+}
+// operands loaded inside the call (the generic tiled kernel's pack loop)
+template <typename H>
+__device__ __forceinline__ void epilogue_pack8(const GemmArgs& g, const Pack<H, 8>& pv, H* Cg, H* Pg, const H* Rg, const H* Gg, int64_t ci,
+                                               int64_t ri, int n_ok) {
+  epilogue_pack8_apply(g, pv, EpiFromMemory<H>{Cg, Rg, Gg, ci, ri}, Cg, Pg, Rg, Gg, ci, ri, n_ok);
+}
+// operands from slot `slot` (wave-uniform) of a batch fetched with epilogue_fetch
+template <typename H, int NP>
+__device__ __forceinline__ void epilogue_pack8(const GemmArgs& g, const Pack<H, 8>& pv, const EpiOperands<NP>& ops, int slot, H* Cg, H* Pg,
+                                               const H* Rg, const H* Gg, int64_t ci, int64_t ri, int n_ok) {
+  epilogue_pack8_apply(g, pv, EpiFromBatch<H, NP>{ops, slot}, Cg, Pg, Rg, Gg, ci, ri, n_ok);
 }

@@ -195,6 +195,26 @@ __device__ __forceinline__ void gemm_glds_body(GemmArgs g, const GemmGroup& grp,
 
   const int fr = lane & 15, fq = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
   int nk = RAGGED ? nk_w : g.K / BK;
+  // bias values of this lane's accumulator columns (acc[i][j][r] belongs to column n0 + wn0 + j*16 + fq*4 + r), fetched BEFORE the K-loop
+  // from clamped addresses: the accumulator-to-LDS pass of the epilogue finds them in registers instead of waiting for them behind the
+  // last tile.  (Older than every DMA of the loop: vector-memory loads retire in issue order, the counted waits below are unaffected.)
+  float bias_r[TN][4];
+#pragma unroll
+  for (int j = 0; j < TN; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bias_r[j][r] = 0.f;
+  if constexpr (MODE == 0) {  // (mode 2 has no registers to spare: see the epilogue)
+    if (g.bias != nullptr && dbg != 4 && (!SPLITK || split + 1 == g.splits)) {  // (split-K: only the finisher runs the epilogue)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int col = n0 + wn0 + j * 16 + fq * 4 + r;
+          const float b = g.bias[min(col, g.N - 1)];
+          bias_r[j][r] = col < g.N ? b : 0.f;
+        }
+    }
+  }
   if constexpr (SPLITK) {  // this workgroup reduces K-tiles [kb, ke) of the product: the operand pointers move, the loop shortens
     static_assert(MODE == 0 && PIPE == 0, "split-K is built for the plain forward / dX loop");
     const int kb = nk * split / g.splits, ke = nk * (split + 1) / g.splits;
@@ -474,30 +494,58 @@ __device__ __forceinline__ void gemm_glds_body(GemmArgs g, const GemmGroup& grp,
   if constexpr (MODE == 2) g.M = g.m_store;  // (operand loads are done: from here on M only guards the stores)
   if (g.c_dtype == H16<E>::DT && g.vecC) {
     constexpr int LDE = WN + 8;
+    constexpr int CPR = WN / 8, NP = WM * CPR / 64, RSTEP = 64 / CPR;  // a lane's NP packs: one column chunk, rows RSTEP apart
     E* Cs = reinterpret_cast<E*>(smem) + wave * WM * LDE;
+    E* Cg = reinterpret_cast<E*>(g.C);
+    E* Pg = reinterpret_cast<E*>(g.P);
+    const E* Rg = reinterpret_cast<const E*>(g.R);
+    const E* Gg = reinterpret_cast<const E*>(g.G);
+    // the packs of G, R and the old C that the rolled loop below consumes: ONE batch of loads (gemm_args.h epilogue_fetch).  Rows >= M are
+    // clamped to the last row, a pack that is not wholly inside the N columns to the row's first pack; those values are never used.
+    // With four packs per lane the batch goes out in front of the accumulator-to-LDS pass and flies under it; the 128-wide tile on four
+    // waves (eight packs, 64 accumulator registers) issues it behind that pass, when the accumulators are dead.
+    // Mode 2 (batched TN products, plain in every caller) keeps its epilogue as it was, bias and operand loads inside the passes: its fp16
+    // instantiation sits at 128 + 68 registers, and with the prefetched bias or the batch (192 + 68) it loses its second workgroup per CU.
+    constexpr bool FETCH_EARLY = NP <= 4, BATCHED_FETCH = MODE != 2;
+    EpiOperands<NP> ops;
+    const int prow0 = m0 + wm0 + lane / CPR, pcol = n0 + wn0 + (lane % CPR) * 8;
+    const int pcol_c = pcol + 8 <= g.N ? pcol : 0, prow_last = max(g.M - 1, 0);
+    auto fetch = [&]() {
+      if (!BATCHED_FETCH || dbg == 5) return;
+      epilogue_fetch<E, NP>(
+          ops, g.beta != 0.f ? Cg : nullptr, Rg, Gg, [&](int k) { return (int64_t)min(prow0 + k * RSTEP, prow_last) * g.ldc + pcol_c; },
+          [&](int k) { return (int64_t)min(prow0 + k * RSTEP, prow_last) * g.ldr + pcol_c; });
+    };
+    if constexpr (FETCH_EARLY) fetch();
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         // acc[i][j][r] = C[wm0 + i*16 + fr][wn0 + j*16 + fq*4 + r]: four consecutive columns -> one 8-byte LDS store
-        const int col = n0 + wn0 + j * 16 + fq * 4;
-        Pack<E, 4> pk;
+        if constexpr (MODE == 2) {  // (as it always was: the bias, if any, is fetched here)
+          const int col = n0 + wn0 + j * 16 + fq * 4;
+          Pack<E, 4> pk;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float bv = (g.bias && dbg != 4 && col + r < g.N) ? g.bias[col + r] : 0.f;
-          pk.v[r] = (E)(g.alpha * acc[i][j][r] + bv);
+          for (int r = 0; r < 4; ++r) {
+            const float bv = (g.bias && dbg != 4 && col + r < g.N) ? g.bias[col + r] : 0.f;
+            pk.v[r] = (E)(g.alpha * acc[i][j][r] + bv);
+          }
+          st_pack<E, 4>(Cs + (i * 16 + fr) * LDE + j * 16 + fq * 4, pk);
+        } else {
+          st_pack<E, 4>(Cs + (i * 16 + fr) * LDE + j * 16 + fq * 4, epilogue_stage4<E>(g.alpha, acc[i][j], bias_r[j]));
         }
-        st_pack<E, 4>(Cs + (i * 16 + fr) * LDE + j * 16 + fq * 4, pk);
       }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
+    if constexpr (!FETCH_EARLY) {
+      __builtin_amdgcn_sched_barrier(0);
+      fetch();
+    }
+    // vmcnt(0) lgkmcnt(0): the wave's own LDS stores AND the batch, in front of the loop.  Without the explicit vmcnt the compiler waits
+    // for the batch at its first use INSIDE the rolled loop, i.e. with vmcnt(0) in every iteration - loads and stores share the counter,
+    // so every iteration would then wait for the previous iteration's stores to be acknowledged: one memory round trip per pack again.
+    __builtin_amdgcn_s_waitcnt(0x0070);
     __builtin_amdgcn_wave_barrier();
-    constexpr int CPR = WN / 8;
-    E* Cg = reinterpret_cast<E*>(g.C);
-    E* Pg = reinterpret_cast<E*>(g.P);
-    const E* Rg = reinterpret_cast<const E*>(g.R);
-    const E* Gg = reinterpret_cast<const E*>(g.G);
 #pragma unroll 1
-    for (int it = 0; it < WM * CPR / 64; ++it) {  // (rolled on purpose: one copy of the epilogue arithmetic)
+    for (int it = 0; it < NP; ++it) {  // (rolled on purpose: one copy of the epilogue arithmetic)
       const int e = it * 64 + lane;
       const int rl = e / CPR, ch = e % CPR;
       const int row = m0 + wm0 + rl, col = n0 + wn0 + ch * 8;
@@ -506,7 +554,8 @@ __device__ __forceinline__ void gemm_glds_body(GemmArgs g, const GemmGroup& grp,
       const int64_t ci = (int64_t)row * g.ldc + col;
       const int64_t ri = (int64_t)row * g.ldr + col;
       if (dbg == 5) continue;
-      epilogue_pack8(g, pv, Cg, Pg, Rg, Gg, ci, ri, g.N - col);
+      if constexpr (BATCHED_FETCH) epilogue_pack8(g, pv, ops, it, Cg, Pg, Rg, Gg, ci, ri, g.N - col);
+      else epilogue_pack8(g, pv, Cg, Pg, Rg, Gg, ci, ri, g.N - col);
     }
     if (stamping) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
