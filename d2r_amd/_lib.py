@@ -15,6 +15,7 @@ F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_GELU, ACT_QUICK_GELU, ACT_TANH_RELU, ACT_SIGMOID = range(7)
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 GRAD_NORM_PARTS, GRAD_NORM_MAX_RANGES = 2048, 16  # D2R_GRAD_NORM_PARTS / D2R_GRAD_NORM_MAX_RANGES of include/d2r_hip.h
+ADAMW_MAX_SEGMENTS, ADAMW_MAX_GROUPS = 4096, 8  # D2R_ADAMW_MAX_SEGMENTS / D2R_ADAMW_MAX_GROUPS of include/d2r_hip.h
 
 vp, i32, i64, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
@@ -99,6 +100,10 @@ class JpegImageDesc(C.Structure):
 
 class JpegSegment(C.Structure):
     _fields_ = [("offset", i64), ("bits", i32), ("chunk0", i32)]
+
+
+class AdamwSeg(C.Structure):  # d2r_adamw_seg: elements [previous end, end) get lr[group] * lr_scale and weight_decay
+    _fields_ = [("end", i64), ("lr_scale", f32), ("weight_decay", f32), ("group", C.c_int32), ("reserved", C.c_int32)]
 
 
 # name -> (restype, argtypes); every symbol include/d2r_hip.h declares
@@ -211,6 +216,10 @@ SIGNATURES = {
     "d2r_adamw_step_dev_clip": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, f32, f32, f32, f32, vp, vp, vp]),
     "d2r_adamw_step_ema": (i32, [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, i64, f32, vp, vp, vp, f32, vp]),
     "d2r_adamw_step_dev_ema": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp]),
+    "d2r_adamw_table_check": (i32, [C.POINTER(AdamwSeg), i32, i64, i32]),
+    "d2r_adamw_step_table": (i32, [vp, vp, vp, vp, vp, i32, i64, i64, vp, i32, i64, C.POINTER(f32), i32, f32, f32, f32, i64, f32, vp, vp,
+                                   vp, f32, vp]),
+    "d2r_adamw_step_table_dev": (i32, [vp, vp, vp, vp, vp, i32, i64, i64, vp, i32, i64, vp, i32, f32, f32, f32, vp, vp, vp, vp, vp]),
     "d2r_swap_f32": (i32, [vp, vp, i64, vp]),
     "d2r_grad_sumsq": (i32, [vp, vp, i32, vp, i64, vp]),
     "d2r_grad_norm_finish": (i32, [vp, i64, f32, vp, f32, vp, vp, vp]),

@@ -526,6 +526,247 @@ extern "C" int d2r_adamw_step_dev_ema(float* w, const float* g, float* m, float*
                       d_hyper, d_skip, d_coef, ema, 0.f, d_ema_one_minus_decay, stream);
 }
 
+// ---- K14 with per-range hyper-parameters: one launch over the flat buffers, {lr scale, weight decay, group} from a device table ----
+// (layer-wise lr decay, no decay on 1-D parameters: an extension beyond the reference.  Several hundred runs of equal
+// hyper-parameters would otherwise be a launch each.)
+extern "C" int d2r_adamw_table_check(const d2r_adamw_seg* host_table, int nseg, int64_t n, int ngroups) {
+  D2R_REQUIRE(host_table, "d2r_adamw_table_check: host_table is NULL");
+  D2R_REQUIRE(nseg >= 1 && nseg <= D2R_ADAMW_MAX_SEGMENTS, "d2r_adamw_table_check: nseg = %d is outside 1..%d", nseg,
+              D2R_ADAMW_MAX_SEGMENTS);
+  D2R_REQUIRE(ngroups >= 1 && ngroups <= D2R_ADAMW_MAX_GROUPS, "d2r_adamw_table_check: ngroups = %d is outside 1..%d", ngroups,
+              D2R_ADAMW_MAX_GROUPS);
+  int64_t prev = 0;
+  for (int s = 0; s < nseg; ++s) {
+    const d2r_adamw_seg& t = host_table[s];
+    D2R_REQUIRE(t.end > prev, "d2r_adamw_table_check: segment %d ends at %lld, not beyond %lld where it begins (ends must increase strictly)",
+                s, (long long)t.end, (long long)prev);
+    D2R_REQUIRE(std::isfinite(t.lr_scale) && t.lr_scale >= 0.f, "d2r_adamw_table_check: segment %d has lr_scale %g (must be finite and >= 0)",
+                s, (double)t.lr_scale);
+    D2R_REQUIRE(std::isfinite(t.weight_decay) && t.weight_decay >= 0.f,
+                "d2r_adamw_table_check: segment %d has weight_decay %g (must be finite and >= 0)", s, (double)t.weight_decay);
+    D2R_REQUIRE(t.group >= 0 && t.group < ngroups, "d2r_adamw_table_check: segment %d names group %d of %d", s, t.group, ngroups);
+    D2R_REQUIRE(t.reserved == 0, "d2r_adamw_table_check: segment %d has reserved = %d (must be 0)", s, t.reserved);
+    prev = t.end;
+  }
+  D2R_REQUIRE(prev == n, "d2r_adamw_table_check: segment %d, the last, ends at %lld but the buffers hold %lld elements", nseg - 1,
+              (long long)prev, (long long)n);
+  return D2R_OK;
+}
+
+struct AdamwGroupLr { float lr[D2R_ADAMW_MAX_GROUPS]; };  // the eager form's per-group lr, by value
+
+// The first segment at or after `lo` whose end lies beyond element i.  The last segment's end is the table's end, which lies beyond
+// every element of a launch, so the answer is at most nseg - 1 and nothing past the table is read.
+__device__ __forceinline__ int adamw_seg_of(const d2r_adamw_seg* __restrict__ t, int lo, int nseg, int64_t i) {
+  int hi = nseg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (t[mid].end > i) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+// lr of group q: row q of d_hyper (hipGraph form), else a select chain over the by-value array (a dynamic index would spill it).
+// q comes from a table the host has checked; it is clamped all the same, so that no table can make this read out of bounds.
+__device__ __forceinline__ float adamw_group_lr(const AdamwGroupLr& a, const float* __restrict__ d_hyper, int ngroups, int q) {
+  q = q < 0 ? 0 : (q >= ngroups ? ngroups - 1 : q);
+  if (d_hyper) return d_hyper[4 * q];
+  float r = a.lr[0];
+#pragma unroll
+  for (int k = 1; k < D2R_ADAMW_MAX_GROUPS; ++k) r = q == k ? a.lr[k] : r;
+  return r;
+}
+
+// What the update needs of an element's hyper-parameters: keep = 1 - lr * wd (decoupled weight decay), step = lr / bc1, with
+// lr = lr[group] * lr_scale.  Three single operations, each rounded on its own (no contraction; fp32 division is correctly rounded),
+// so the values are the same bits whether a workgroup derived them once for a whole segment or a lane for one element.
+struct AdamwHyp { float keep, step; };
+__device__ __forceinline__ AdamwHyp adamw_hyp(float lr_group, float lr_scale, float wd, float bc1) {
+#pragma clang fp contract(off)
+  const float lr = lr_group * lr_scale;
+  AdamwHyp h;
+  h.keep = 1.f - lr * wd;
+  h.step = lr / bc1;
+  return h;
+}
+
+// A workgroup's pass covers the 1,024 contiguous elements [begin + 1024 p, +1024): 256 lanes x one 16-byte pack, and a workgroup
+// takes CONSECUTIVE passes (an equal share of them per workgroup, not a grid stride), so it walks through the table once: it finds
+// the segment of its first element by a binary search all lanes run alike (uniform addresses), keeps that segment's end and values
+// in registers, and looks again only when a span starts beyond that end - the model's segments are hundreds of passes long.  When
+// the span ends inside the segment every lane takes the uniform values.  Otherwise each lane searches on from there for its pack,
+// and a pack that a boundary cuts resolves per element.  Whatever path found the hyper-parameters, the update below is ONE piece of
+// code, compiled without floating-point contraction: a copy the compiler makes of it for one path cannot round differently from
+// another (the note in adamw_kernel on what contraction does to the same source in different loops), and a pack cut by `end` goes
+// through it masked instead of through a scalar loop.  So an element's result does not depend on how [0, n) is cut into launches -
+// replicas and the sharded step rely on that.
+template <typename H, bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void adamw_table_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, H* __restrict__ w16, int64_t begin, int64_t end,
+                                                          const d2r_adamw_seg* __restrict__ table, int nseg, AdamwGroupLr glr,
+                                                          int ngroups, float b1, float b2, float eps, float bc1, float bc2_sqrt,
+                                                          float gscale, const float* __restrict__ d_hyper,
+                                                          const int* __restrict__ d_skip, const float* __restrict__ d_coef,
+                                                          float* __restrict__ ema, float omd, const float* __restrict__ d_omd) {
+  if (d_skip && *d_skip) return;  // overflowed loss-scaled gradients: this step is dropped
+  if (d_hyper) {  // the step's scalars are the same in every row
+    bc1 = d_hyper[1];
+    bc2_sqrt = d_hyper[2];
+    gscale = d_hyper[3];
+  }
+  float coef = 1.f;
+  if constexpr (CLIP) coef = *d_coef;
+  if constexpr (EMA) {
+    if (d_omd) omd = *d_omd;
+  }
+  const int64_t npass = (end - begin + 1023) / 1024;
+  const int64_t per = (npass + gridDim.x - 1) / gridDim.x;
+  const int64_t p0 = (int64_t)blockIdx.x * per, p1 = p0 + per < npass ? p0 + per : npass;
+  if (p0 >= p1) return;
+  auto hyp_of = [&](int s) { return adamw_hyp(adamw_group_lr(glr, d_hyper, ngroups, table[s].group), table[s].lr_scale, table[s].weight_decay, bc1); };
+  int s0 = adamw_seg_of(table, 0, nseg, begin + p0 * 1024);
+  int64_t e0 = table[s0].end;
+  AdamwHyp hu = hyp_of(s0);
+  for (int64_t p = p0; p < p1; ++p) {
+    const int64_t span = begin + p * 1024;
+    if (span >= e0) {  // the workgroup has left its segment (all lanes alike)
+      s0 = adamw_seg_of(table, s0 + 1 < nseg ? s0 + 1 : nseg - 1, nseg, span);
+      e0 = table[s0].end;
+      hu = hyp_of(s0);
+    }
+    const int64_t i = span + (int64_t)threadIdx.x * 4;
+    if (i >= end) continue;
+    const bool full = i + 4 <= end;
+    Pack<float, 4> pw, pg, pm, pv, pe;
+    if (full) {
+      pw = ld_pack<float, 4>(w + i), pg = ld_pack<float, 4>(g + i), pm = ld_pack<float, 4>(m + i), pv = ld_pack<float, 4>(v + i);
+      if constexpr (EMA) pe = ld_pack<float, 4>(ema + i);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool ok = i + j < end;
+        pw.v[j] = ok ? w[i + j] : 0.f, pg.v[j] = ok ? g[i + j] : 0.f, pm.v[j] = ok ? m[i + j] : 0.f, pv.v[j] = ok ? v[i + j] : 0.f;
+        if constexpr (EMA) pe.v[j] = ok ? ema[i + j] : 0.f;
+      }
+    }
+    // ---- lookup: the hyper-parameters of the pack's four elements
+    AdamwHyp h[4];
+    const int64_t span_last = (span + 1024 < end ? span + 1024 : end) - 1;
+    if (e0 > span_last) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) h[j] = hu;
+    } else {
+      int s = adamw_seg_of(table, s0, nseg, i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (i + j < end)
+          while (s < nseg - 1 && table[s].end <= i + j) ++s;
+        h[j] = hyp_of(s);
+      }
+    }
+    // ---- the update: the one arithmetic body
+    {
+#pragma clang fp contract(off)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float gi = pg.v[j] * gscale;
+        if constexpr (CLIP) gi = gi * coef;
+        float wi = pw.v[j] * h[j].keep;  // decoupled weight decay
+        const float mi = b1 * pm.v[j] + (1.f - b1) * gi;
+        const float vi = b2 * pv.v[j] + (1.f - b2) * gi * gi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        wi = wi - h[j].step * (mi / denom);
+        pw.v[j] = wi, pm.v[j] = mi, pv.v[j] = vi;
+        if constexpr (EMA) pe.v[j] = pe.v[j] + omd * (wi - pe.v[j]);
+      }
+    }
+    Pack<H, 4> ph;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ph.v[j] = (H)pw.v[j];
+    if (full) {
+      st_pack<float, 4>(w + i, pw);
+      st_pack<float, 4>(m + i, pm);
+      st_pack<float, 4>(v + i, pv);
+      if constexpr (EMA) st_pack<float, 4>(ema + i, pe);
+      if (w16) st_pack<H, 4>(w16 + i, ph);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (i + j < end) {
+          w[i + j] = pw.v[j], m[i + j] = pm.v[j], v[i + j] = pv.v[j];
+          if constexpr (EMA) ema[i + j] = pe.v[j];
+          if (w16) w16[i + j] = ph.v[j];
+        }
+      }
+    }
+  }
+}
+
+static int adamw_table_launch(const char* name, float* w, const float* g, float* m, float* v, void* w16, int w16_dtype, int64_t begin,
+                              int64_t end, const d2r_adamw_seg* d_table, int nseg, int64_t n, const AdamwGroupLr& glr, int ngroups,
+                              float b1, float b2, float eps, float bc1, float bc2s, float gscale, const float* d_hyper,
+                              const int* d_skip, const float* d_coef, float* ema, float omd, const float* d_omd, void* stream) {
+  D2R_REQUIRE(w && g && m && v && d_table, "%s: bad arguments (a NULL pointer)", name);
+  D2R_REQUIRE(nseg >= 1 && nseg <= D2R_ADAMW_MAX_SEGMENTS, "%s: nseg = %d is outside 1..%d", name, nseg, D2R_ADAMW_MAX_SEGMENTS);
+  D2R_REQUIRE(ngroups >= 1 && ngroups <= D2R_ADAMW_MAX_GROUPS, "%s: ngroups = %d is outside 1..%d", name, ngroups, D2R_ADAMW_MAX_GROUPS);
+  D2R_REQUIRE(begin >= 0 && begin <= end && end <= n, "%s: [begin, end) = [%lld, %lld) must lie inside the table's [0, %lld)", name,
+              (long long)begin, (long long)end, (long long)n);
+  D2R_REQUIRE(begin % 4 == 0, "%s: begin = %lld must be a multiple of 4 (16-byte packs)", name, (long long)begin);
+  D2R_REQUIRE(d2r_aligned16(w) && d2r_aligned16(g) && d2r_aligned16(m) && d2r_aligned16(v), "%s: pointers must be 16-byte aligned", name);
+  D2R_REQUIRE(!w16 || ((reinterpret_cast<uintptr_t>(w16) & 7u) == 0 && d2r_is16(w16_dtype)),
+              "%s: the 16-bit shadow must be 8-byte aligned and D2R_BF16 or D2R_F16 (got dtype %d)", name, w16_dtype);
+  D2R_REQUIRE(!ema || (d2r_aligned16(ema) && ema != w), "%s: ema must be a 16-byte aligned buffer of its own (not w)", name);
+  D2R_REQUIRE((reinterpret_cast<uintptr_t>(d_table) & 7u) == 0, "%s: d_table must be 8-byte aligned", name);
+  if (end == begin) return D2R_OK;
+  const int64_t npass = (end - begin + 1023) / 1024;
+  const int cap = g_adamw_blocks > 0 ? g_adamw_blocks : 2048;
+  const int blocks = (int)(npass < cap ? npass : cap);
+#define D2R_ADAMW_TABLE_LAUNCH(H, CLIP, EMA)                                                                                        \
+  hipLaunchKernelGGL((adamw_table_kernel<H, CLIP, EMA>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, g, m, v, (H*)w16, begin, \
+                     end, d_table, nseg, glr, ngroups, b1, b2, eps, bc1, bc2s, gscale, d_hyper, d_skip, d_coef, ema, omd, d_omd)
+#define D2R_ADAMW_TABLE_LAUNCH_EMA(H, CLIP)         \
+  if (ema) D2R_ADAMW_TABLE_LAUNCH(H, CLIP, true); \
+  else D2R_ADAMW_TABLE_LAUNCH(H, CLIP, false)
+  if (w16 && w16_dtype == D2R_F16) {
+    if (d_coef) { D2R_ADAMW_TABLE_LAUNCH_EMA(f16_t, true); }
+    else { D2R_ADAMW_TABLE_LAUNCH_EMA(f16_t, false); }
+  } else {
+    if (d_coef) { D2R_ADAMW_TABLE_LAUNCH_EMA(bf16_t, true); }
+    else { D2R_ADAMW_TABLE_LAUNCH_EMA(bf16_t, false); }
+  }
+#undef D2R_ADAMW_TABLE_LAUNCH_EMA
+#undef D2R_ADAMW_TABLE_LAUNCH
+  return d2r_check_launch(name);
+}
+
+extern "C" int d2r_adamw_step_table(float* w, const float* g, float* m, float* v, void* w16, int w16_dtype, int64_t begin, int64_t end,
+                                    const d2r_adamw_seg* d_table, int nseg, int64_t n, const float* lr, int ngroups, float beta1,
+                                    float beta2, float eps, int64_t step, float grad_scale, const int* d_skip, const float* d_coef,
+                                    float* ema, float ema_one_minus_decay, void* stream) {
+  D2R_REQUIRE(lr && step >= 1, "d2r_adamw_step_table: bad arguments (lr is NULL or step < 1)");
+  D2R_REQUIRE(ngroups >= 1 && ngroups <= D2R_ADAMW_MAX_GROUPS, "d2r_adamw_step_table: ngroups = %d is outside 1..%d", ngroups,
+              D2R_ADAMW_MAX_GROUPS);
+  D2R_REQUIRE(!ema || (ema_one_minus_decay >= 0.f && ema_one_minus_decay <= 1.f), "d2r_adamw_step_table: 1 - decay = %g is outside [0, 1]",
+              (double)ema_one_minus_decay);
+  AdamwGroupLr glr = {};
+  for (int q = 0; q < ngroups; ++q) glr.lr[q] = lr[q];
+  // double on the host, rounded once, as d2r_adamw_step does: FusedAdamW.stage_hyper computes the very same values
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  return adamw_table_launch("d2r_adamw_step_table", w, g, m, v, w16, w16_dtype, begin, end, d_table, nseg, n, glr, ngroups, beta1, beta2,
+                            eps, bc1, bc2s, grad_scale, nullptr, d_skip, d_coef, ema, ema_one_minus_decay, nullptr, stream);
+}
+extern "C" int d2r_adamw_step_table_dev(float* w, const float* g, float* m, float* v, void* w16, int w16_dtype, int64_t begin,
+                                        int64_t end, const d2r_adamw_seg* d_table, int nseg, int64_t n, const float* d_hyper,
+                                        int ngroups, float beta1, float beta2, float eps, const int* d_skip, const float* d_coef,
+                                        float* ema, const float* d_ema_one_minus_decay, void* stream) {
+  D2R_REQUIRE(d_hyper, "d2r_adamw_step_table_dev: d_hyper is NULL");
+  D2R_REQUIRE(!ema || d_ema_one_minus_decay, "d2r_adamw_step_table_dev: d_ema_one_minus_decay is NULL");
+  const AdamwGroupLr glr = {};
+  return adamw_table_launch("d2r_adamw_step_table_dev", w, g, m, v, w16, w16_dtype, begin, end, d_table, nseg, n, glr, ngroups, beta1,
+                            beta2, eps, 1.f, 1.f, 1.f, d_hyper, d_skip, d_coef, ema, 0.f, d_ema_one_minus_decay, stream);
+}
+
 // ---- a[i] <-> b[i] over two disjoint fp32 ranges in one pass (evaluation on the averaged weights: FusedAdamW.ema_weights) -----
 __global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n, int vec) {
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (int64_t)gridDim.x * blockDim.x;

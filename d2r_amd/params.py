@@ -14,7 +14,9 @@ reference stay outside the store and are never updated nor all-reduced (AdamW sk
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import math
+import re
 from typing import Dict, List, Optional
 
 import torch
@@ -43,6 +45,67 @@ def group_of(name: str) -> int:
     if "vision" in name:
         return 2
     return 0
+
+
+_TEXT_LAYER = re.compile(r"model\.encoder\.text_layer\.(\d+)\.")
+_VISION_LAYER = re.compile(r"model\.encoder\.vision_layers\.(\d+)\.")
+
+
+def layer_lr_scale(name: str, n_text_layers: int, n_vision_layers: int, decay: float) -> float:
+    """Layer-wise learning-rate decay, BEiT's convention: a pretrained tower of L encoder layers has the layer ids 0 (embeddings,
+    CLIP's pre-LayerNorm), 1..L (encoder layer i has id i + 1) and L + 1 (everything above it), and a parameter of layer id k
+    learns at decay ** (L + 1 - k) of its group's rate.  Everything that is not part of a pretrained tower - self_text, self_vision,
+    the poolers, both interaction modules, block_fusion, fc - has scale 1.  Anchored prefixes, not substrings: the interaction
+    modules' ...glac.text_cls_pool... contains "text" and is no part of the text tower."""
+    m = _TEXT_LAYER.match(name)
+    if m is not None:
+        layers, lid = n_text_layers, int(m.group(1)) + 1
+    elif name.startswith("model.text_embeddings."):
+        layers, lid = n_text_layers, 0
+    else:
+        m = _VISION_LAYER.match(name)
+        if m is not None:
+            layers, lid = n_vision_layers, int(m.group(1)) + 1
+        elif name.startswith(("model.vision_embeddings.", "model.vision_pre_layrnorm.")):
+            layers, lid = n_vision_layers, 0
+        else:
+            return 1.0
+    return float(decay) ** (layers + 1 - lid)
+
+
+def tower_layers(names):
+    """(text, vision): the number of encoder layers of each pretrained tower among the parameter names (highest index + 1)."""
+    out = []
+    for rx in (_TEXT_LAYER, _VISION_LAYER):
+        ids = [int(m.group(1)) for m in map(rx.match, names) if m is not None]
+        out.append(max(ids) + 1 if ids else 0)
+    return tuple(out)
+
+
+def build_adamw_table(entries, n: int, hyper):
+    """The segments of d2r_adamw_step_table for a flat buffer of n elements: [(end, lr_scale, weight_decay, group)], covering
+    [0, n) with strictly increasing ends.  entries: ParamStore.entries, (name, param, offset, numel, group) in offset order;
+    hyper(name, param, group) -> (lr_scale, weight_decay).  A parameter's segment runs up to the next parameter's offset: the
+    alignment padding behind it (w = g = 0 there, and it stays 0 under any hyper-parameters) belongs to it.  Neighbours with equal
+    (group, lr_scale, weight_decay) merge into one segment."""
+    segs = []
+    for k, (name, param, off, numel, group) in enumerate(entries):
+        end = entries[k + 1][2] if k + 1 < len(entries) else n
+        if not off + numel <= end <= n:
+            raise ValueError(f"entry {name!r} at [{off}, {off + numel}) overlaps its successor at {end} or the end of the buffer {n}")
+        if k == 0 and off != 0:
+            raise ValueError(f"the first entry {name!r} starts at {off}, not at 0")
+        lr_scale, wd = hyper(name, param, group)
+        key = (int(group), float(lr_scale), float(wd))
+        if end == (segs[-1][0] if segs else 0):
+            continue  # an empty parameter
+        if segs and segs[-1][1:] == (key[1], key[2], key[0]):
+            segs[-1] = (end,) + segs[-1][1:]
+        else:
+            segs.append((end, key[1], key[2], key[0]))
+    if not segs or segs[-1][0] != n:
+        raise ValueError(f"the entries do not cover [0, {n})")
+    return segs
 
 
 class FusedLinear:
@@ -120,6 +183,8 @@ class ParamStore:
         for g, (a, b) in self.group_ranges.items():  # groups must be contiguous ranges
             assert all(a <= o < b for _, _, o, _, gg in self.entries if gg == g)
         self.n = off
+        # encoder layers of the two pretrained towers (layer-wise lr decay: FusedAdamW(layer_lr_decay=...))
+        self.n_text_layers, self.n_vision_layers = tower_layers([e[0] for e in self.entries])
         self.flat_w = torch.zeros(off, dtype=torch.float32, device=device)
         self.flat_g = torch.zeros(off, dtype=torch.float32, device=device)
         self.flat_lp = torch.zeros(off, dtype=compute_dtype, device=device) if compute_dtype in (torch.bfloat16, torch.float16) else None
@@ -225,11 +290,27 @@ class FusedAdamW:
     use_num_updates=True.  ``ema_reset()`` seeds it from the weights, ``ema_weights()`` swaps it in for evaluation.  A step the fp16
     overflow flag drops leaves ema untouched on the device; the host learns of the drop one step late (_scaler_consume), so the t
     of the step after a dropped one is one too high - the same one-step lag the bias correction has, and no sync removes it.
-    Buffers (BatchNorm running statistics) are not averaged.  None or 0: off, and then nothing here differs from the plain step."""
+    Buffers (BatchNorm running statistics) are not averaged.  None or 0: off, and then nothing here differs from the plain step.
+
+    layer_lr_decay = D in (0, 1) scales the learning rate of the pretrained towers' parameters layer by layer (layer_lr_scale),
+    decay_exempt_1d = True gives parameters with dim() <= 1 (biases, LayerNorm / BatchNorm weight and bias, CLIP's class_embedding)
+    weight decay 0 - both extensions beyond the reference, and both hyper-parameters per PARAMETER inside a group.  With either on,
+    the step is ONE launch over the flat buffers (per owned range under the sharded optimiser) that reads {lr scale, weight decay,
+    group} per element range from a device table (d2r_adamw_step_table; ``table`` holds the segments, built once - the schedule
+    still moves the four group rates, the table is static).  n_text_layers / n_vision_layers: the towers' depths, by default the
+    store's.  layer_lr_decay None or 1 and decay_exempt_1d False: off, the launch per group as before."""
 
     def __init__(self, store: ParamStore, lr: float, fc_lr: float = 5e-2, weight_decay: float = 1e-2,
                  betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: Optional[float] = None,
-                 ema_decay: Optional[float] = None):
+                 ema_decay: Optional[float] = None, layer_lr_decay: Optional[float] = None, decay_exempt_1d: bool = False,
+                 n_text_layers: Optional[int] = None, n_vision_layers: Optional[int] = None):
+        if layer_lr_decay is not None and not 0 < layer_lr_decay <= 1:
+            raise ValueError(f"layer_lr_decay must be None or in (0, 1], got {layer_lr_decay}")
+        if not (weight_decay >= 0 and math.isfinite(weight_decay)):
+            raise ValueError(f"weight_decay must be finite and >= 0, got {weight_decay}")
+        self.layer_lr_decay = float(layer_lr_decay) if layer_lr_decay is not None and layer_lr_decay != 1 else None
+        self.decay_exempt_1d = bool(decay_exempt_1d)
+        self.table = None
         if max_grad_norm is not None and not max_grad_norm >= 0:
             raise ValueError(f"max_grad_norm must be None or >= 0, got {max_grad_norm}")
         if ema_decay is not None and not 0 <= ema_decay < 1:
@@ -269,6 +350,45 @@ class FusedAdamW:
             self._ema_omd_cpu = torch.zeros(1, dtype=torch.float32)  # pageable on purpose, see stage_hyper
             self._ema_omd_dev = torch.zeros(1, dtype=torch.float32, device=store.flat_w.device)
             self.ema_reset()
+        if self.layer_lr_decay is not None or self.decay_exempt_1d:
+            self._build_table(store.n_text_layers if n_text_layers is None else int(n_text_layers),
+                              store.n_vision_layers if n_vision_layers is None else int(n_vision_layers))
+
+    # -- per-parameter hyper-parameters -----------------------------------------------------------------
+    def _build_table(self, n_text_layers: int, n_vision_layers: int):
+        """Builds the segment table once, has the library check the host copy, uploads it (eagerly: never inside a capture)."""
+        st = self.store
+        if len(self.param_groups) > _lib.ADAMW_MAX_GROUPS:
+            raise ValueError(f"{len(self.param_groups)} parameter groups, the table kernel takes {_lib.ADAMW_MAX_GROUPS}")
+        index = {g: i for i, (g, _) in enumerate(sorted(st.group_ranges.items()))}  # optimiser group -> row of param_groups
+        decay = 1.0 if self.layer_lr_decay is None else self.layer_lr_decay
+
+        def hyper(name, param, row):
+            return (layer_lr_scale(name, n_text_layers, n_vision_layers, decay),
+                    0.0 if self.decay_exempt_1d and param.dim() <= 1 else self.param_groups[row]["weight_decay"])
+
+        self.table = build_adamw_table([(n, p, o, k, index[g]) for n, p, o, k, g in st.entries], st.n, hyper)
+        self.tower_lr_scales = tuple(min([layer_lr_scale(n, n_text_layers, n_vision_layers, decay) for n, *_ in st.entries
+                                          if rx.match(n) or n.startswith(pre)] or [1.0])
+                                     for rx, pre in ((_TEXT_LAYER, "model.text_embeddings."),
+                                                     (_VISION_LAYER, ("model.vision_embeddings.", "model.vision_pre_layrnorm."))))
+        self._set_table(self.table)
+
+    def _set_table(self, segs):
+        """Has the library check the host copy of the segments [(end, lr_scale, weight_decay, row of param_groups)], then uploads it."""
+        st = self.store
+        self.table = list(segs)
+        if len(self.table) > _lib.ADAMW_MAX_SEGMENTS:
+            raise ValueError(f"{len(self.table)} segments, the table kernel takes {_lib.ADAMW_MAX_SEGMENTS}")
+        arr = (_lib.AdamwSeg * len(self.table))(*[_lib.AdamwSeg(e, s, wd, g, 0) for e, s, wd, g in self.table])
+        _lib.call("d2r_adamw_table_check", arr, len(self.table), st.n, len(self.param_groups))
+        self._table_dev = torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(st.flat_w.device)
+        self._table_lr = (ctypes.c_float * len(self.param_groups))()
+
+    def _table_args(self, a, b):
+        st = self.store
+        return (st.flat_w.data_ptr(), st.flat_g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                None if st.flat_lp is None else st.flat_lp.data_ptr(), st.lp_dtype, a, b, self._table_dev.data_ptr(), len(self.table), st.n)
 
     def zero_grad(self, set_to_none: bool = False):
         self.store.zero_grad()
@@ -434,7 +554,15 @@ class FusedAdamW:
         self.step_count += 1
         st = self.store
         omd = ema_one_minus_decay(self.ema_decay, self.step_count) if self.ema is not None else None
-        for pg in self.param_groups:
+        if self.table is not None:  # one launch per owned range, hyper-parameters per element range from the device table
+            for i, pg in enumerate(self.param_groups):
+                self._table_lr[i] = pg["lr"]
+            for a, b in ([(0, st.n)] if self.element_ranges is None else self.element_ranges):
+                if b > a:
+                    _lib.call("d2r_adamw_step_table", *self._table_args(a, b), self._table_lr, len(self.param_groups), self.betas[0],
+                              self.betas[1], self.eps, self.step_count, self.grad_scale / used, skip, coef,
+                              None if self.ema is None else self.ema.data_ptr(), omd or 0.0, _stream())
+        for pg in (self.param_groups if self.table is None else ()):
             for a, b in self._owned(pg["range"]):
                 lp = None if st.flat_lp is None else st.flat_lp.data_ptr() + 2 * a
                 args = (st.flat_w.data_ptr() + 4 * a, st.flat_g.data_ptr() + 4 * a, self.m.data_ptr() + 4 * a, self.v.data_ptr() + 4 * a,
@@ -505,6 +633,11 @@ class FusedAdamW:
             skip = self._scaler["flag"].data_ptr()
         if self.max_grad_norm is not None:  # unscale factor from d_hyper (every group holds the same), max_norm baked in
             coef = self._clip_coef(0.0, dev.data_ptr() + 12, skip)
+        if self.table is not None:
+            _lib.call("d2r_adamw_step_table_dev", *self._table_args(0, st.n), dev.data_ptr(), len(self.param_groups), self.betas[0],
+                      self.betas[1], self.eps, skip, coef, None if self.ema is None else self.ema.data_ptr(),
+                      None if self.ema is None else self._ema_omd_dev.data_ptr(), _stream())
+            return
         for i, pg in enumerate(self.param_groups):
             a, b = pg["range"]
             if b <= a:

@@ -15,12 +15,14 @@ allowed), --write_path writes the per-sample predictions as JSON Lines (MSDTrain
 --ema_decay D averages the weights inside the AdamW launch; the dev / test passes and best_model.pth use the average.
 --label_smoothing E / --class_weights {none | balanced | W0,W1,...} are the options of the cross entropy (inside its kernels).
 --aug_crop_scale LO / --aug_flip P (with --data_path) augment the training images on the device (d2r_amd.augment).
+--layer_lr_decay D / --wd_exempt_1d / --weight_decay W: AdamW hyper-parameters per parameter, still one launch (d2r_adamw_step_table).
 """
 from __future__ import annotations
 
 import argparse
 import contextlib
 import logging
+import math
 import os
 import random
 
@@ -50,6 +52,20 @@ def _ema_decay(text):
     v = float(text)
     if not 0 <= v < 1:
         raise argparse.ArgumentTypeError(f"must be in [0, 1) (0 = no averaging), got {text}")
+    return v
+
+
+def _layer_lr_decay(text):
+    v = float(text)
+    if not 0 < v <= 1:
+        raise argparse.ArgumentTypeError(f"must be in (0, 1] (1 = off), got {text}")
+    return v
+
+
+def _weight_decay(text):
+    v = float(text)
+    if not (v >= 0 and math.isfinite(v)):
+        raise argparse.ArgumentTypeError(f"must be finite and >= 0, got {text}")
     return v
 
 
@@ -177,6 +193,13 @@ def build_parser():
                    "updated inside the AdamW launch; the dev / test passes run on it and best_model.pth holds it (0 = off, the "
                    "reference's behaviour).  The decay warms up as torch_ema does with use_num_updates: step t uses "
                    "min(ema_decay, (1 + t) / (10 + t)), always, so a short run does not keep averaging its random initialisation")
+    p.add_argument("--layer_lr_decay", default=1.0, type=_layer_lr_decay, help="layer-wise learning-rate decay of the two pretrained "
+                   "towers (BEiT's convention): encoder layer i of L learns at D ** (L - i) of its group's rate, the embeddings at "
+                   "D ** (L + 1), everything above the towers at the full rate; in (0, 1], 1 = off, the reference's behaviour")
+    p.add_argument("--wd_exempt_1d", action="store_true", help="no weight decay on parameters with one dimension or none: biases, "
+                   "LayerNorm / BatchNorm weight and bias, CLIP's class embedding (off = the reference's behaviour)")
+    p.add_argument("--weight_decay", default=1e-2, type=_weight_decay, help="AdamW's decoupled weight decay, finite and >= 0 "
+                   "(1e-2 = the reference's)")
     p.add_argument("--label_smoothing", default=0.0, type=_label_smoothing, help="label smoothing of the cross entropy, in [0, 1), as "
                    "torch.nn.CrossEntropyLoss(label_smoothing=) (0 = off, the reference's behaviour); training, dev and test loss alike")
     p.add_argument("--class_weights", default="none", type=str, help="per-class weights of the cross entropy, as "
@@ -331,6 +354,9 @@ def main(argv=None):
     if args.ema_decay and args.only_test:
         logger.info("--ema_decay is ignored with --only_test: the checkpoint already holds the weights that were saved")
         args.ema_decay = 0.0
+    if args.only_test and (args.layer_lr_decay != 1.0 or args.wd_exempt_1d or args.weight_decay != 1e-2):
+        logger.info("--layer_lr_decay / --wd_exempt_1d / --weight_decay are ignored with --only_test: no optimiser step is taken")
+        args.layer_lr_decay, args.wd_exempt_1d, args.weight_decay = 1.0, False, 1e-2
     if class_weights == "balanced":
         try:
             class_weights = balanced_class_weights(train_label_counts(args, None if args.data_path is None else files[0]))

@@ -10,7 +10,8 @@ state-dict key names (:210-216).  Differences, all deliberate (SURVEY.md Appendi
   * ``shutil.rmtree("./output")`` (:149) is opt-in (``args.cleanup_output``);
   * optional data parallelism (args.world_size > 1 via torch.distributed, see d2r_amd.dp);
   * optional extensions: gradient clipping (args.max_grad_norm) and a weight EMA (args.ema_decay: evaluate() / test() run on
-    the averaged weights and best_model.pth holds them; BatchNorm running statistics stay the live ones);
+    the averaged weights and best_model.pth holds them; BatchNorm running statistics stay the live ones), layer-wise lr decay and
+    no weight decay on 1-D parameters (args.layer_lr_decay, args.wd_exempt_1d), the weight decay itself (args.weight_decay);
   * optional image augmentation of the TRAINING batches (``augmenter``, d2r_amd.augment: random resized crop and flip on the
     device; a CachedLoader carries its own); evaluate() / test() / predict() never augment;
   * evaluate() / test() count a confusion matrix on the device (d2r_confusion_add) instead of copying labels and predictions to
@@ -159,9 +160,11 @@ class MSDTrainer:
         self.store = ParamStore(self.model, dtype)
         from . import configure_runtime
         configure_runtime()
-        self.optimizer = FusedAdamW(self.store, lr=self.args.lr, fc_lr=5e-2, weight_decay=1e-2,
+        self.optimizer = FusedAdamW(self.store, lr=self.args.lr, fc_lr=5e-2, weight_decay=float(getattr(self.args, "weight_decay", 1e-2)),
                                     max_grad_norm=getattr(self.args, "max_grad_norm", None) or None,
-                                    ema_decay=getattr(self.args, "ema_decay", None) or None)
+                                    ema_decay=getattr(self.args, "ema_decay", None) or None,
+                                    layer_lr_decay=getattr(self.args, "layer_lr_decay", None) or None,
+                                    decay_exempt_1d=bool(getattr(self.args, "wd_exempt_1d", False)))
         if dtype == torch.float16:  # fp16 activation gradients need a scaled loss (AMP's GradScaler, here inside the optimiser)
             self.optimizer.enable_loss_scaling()
         shard = bool(getattr(self.args, "dp_shard_optimizer", False))
@@ -209,6 +212,11 @@ class MSDTrainer:
             self.logger.info("  Weight EMA: decay %g with warm-up min(decay, (1 + t) / (10 + t)); %d bytes of device memory "
                              "(4 per live parameter); evaluation and best_model.pth use the averaged weights",
                              self.optimizer.ema_decay, 4 * self.store.n)
+        if self.optimizer.table is not None:
+            self.logger.info("  AdamW hyper-parameters per parameter: %d segments in one launch (layer_lr_decay %s, weight decay %g%s); "
+                             "smallest lr scale: text tower %g, vision tower %g", len(self.optimizer.table),
+                             self.optimizer.layer_lr_decay, self.optimizer.param_groups[0]["weight_decay"],
+                             ", none on 1-D parameters" if self.optimizer.decay_exempt_1d else "", *self.optimizer.tower_lr_scales)
         augmenter = self.augmenter or getattr(self.train_data, "augmenter", None)
         if augmenter is not None:
             self.logger.info("  Image augmentation of the training batches: %s", augmenter.describe())

@@ -767,6 +767,49 @@ int d2r_adamw_step_dev_ema(float* w, const float* g, float* m, float* v, void* w
                            const float* d_hyper, float beta1, float beta2, float eps, float weight_decay,
                            const int* d_skip /*or NULL*/, const float* d_coef /*or NULL*/, float* ema,
                            const float* d_ema_one_minus_decay, void* stream);
+/* Per-parameter hyper-parameters (layer-wise learning-rate decay, no weight decay on biases and normalisation parameters) - an
+ * extension beyond the reference, whose four groups each have one lr and one weight decay.  ONE launch over the flat buffers
+ * replaces the launch per group of the entry points above: a small device table gives {lr scale, weight decay, group} per element
+ * range, the per-step scalars still arrive per group.
+ * Segment s covers the elements [end[s-1], end[s]) of the flat buffers, end[-1] = 0; the ends are strictly increasing and the last
+ * one is the buffers' length.  `reserved` must be 0. */
+#define D2R_ADAMW_MAX_SEGMENTS 4096 /* segments of one table (the full model needs at most one per parameter) */
+#define D2R_ADAMW_MAX_GROUPS 8      /* groups a table may name */
+typedef struct {
+  int64_t end;        /* one past the segment's last element */
+  float lr_scale;     /* finite, >= 0: the element's lr is lr[group] * lr_scale (one fp32 multiply, so 1 gives lr[group] itself) */
+  float weight_decay; /* finite, >= 0 */
+  int32_t group;      /* in [0, ngroups) */
+  int32_t reserved;   /* 0 */
+} d2r_adamw_seg;
+/* Host only: enqueues nothing and needs no GPU.  Refuses (D2R_ERR_INVALID, d2r_last_error names the offending segment) an nseg
+ * outside 1..D2R_ADAMW_MAX_SEGMENTS, an ngroups outside 1..D2R_ADAMW_MAX_GROUPS, ends that are not strictly increasing, a last end
+ * != n, a non-finite or negative lr_scale or weight_decay, a group outside [0, ngroups) and a non-zero reserved - the host copy of a
+ * descriptor is checked before anything reads its device copy, as d2r_jpeg_decode checks h_desc.  The step entry points below
+ * cannot read d_table; they trust a table that passed here. */
+int d2r_adamw_table_check(const d2r_adamw_seg* host_table, int nseg, int64_t n, int ngroups);
+/* Extends d2r_adamw_step_ema (and with it d2r_adamw_step / d2r_adamw_step_clip: d_coef and ema are both optional here).
+ * w, g, m, v, w16 and ema are the BASE pointers of the whole flat buffers (element 0), [begin, end) is the absolute element range
+ * this launch updates: begin % 4 == 0 (the sharded optimiser's stripes are 16-byte aligned), end arbitrary,
+ * 0 <= begin <= end <= n, n = the table's last end as given to d2r_adamw_table_check.  d_table: device copy of the checked table.
+ * lr: HOST float[ngroups], the scheduled learning rate of each group.  Element i in segment s of group q is updated as
+ * d2r_adamw_step updates an element, with lr = lr[q] * lr_scale[s] and weight_decay[s].  The arithmetic of an element is one piece
+ * of code compiled without floating-point contraction, whichever lookup found its hyper-parameters and wherever it lies in
+ * [begin, end) (the last (end - begin) % 4 elements go through it as a masked pack): the result does not depend on how [0, n) is
+ * cut into launches, bit for bit.  lr_scale == 0 leaves w as it is and still updates m, v (and ema, the shadow).
+ * A refused call writes nothing; begin == end launches nothing. */
+int d2r_adamw_step_table(float* w, const float* g, float* m, float* v, void* w16 /*or NULL*/, int w16_dtype, int64_t begin,
+                         int64_t end, const d2r_adamw_seg* d_table, int nseg, int64_t n, const float* lr, int ngroups, float beta1,
+                         float beta2, float eps, int64_t step, float grad_scale, const int* d_skip /*or NULL*/,
+                         const float* d_coef /*or NULL*/, float* ema /*or NULL*/, float ema_one_minus_decay, void* stream);
+/* hipGraph-capturable form, extends d2r_adamw_step_dev_ema: d_hyper = device float[ngroups][4], row q = {lr, 1-beta1^t,
+ * sqrt(1-beta2^t), grad_scale} of group q (the layout d2r_adamw_step_dev reads one row of).  lr is read from the row of the
+ * element's group; the bias corrections and grad_scale belong to the step, not to a group, and are read from row 0.
+ * d_ema_one_minus_decay: device float, read when ema is given. */
+int d2r_adamw_step_table_dev(float* w, const float* g, float* m, float* v, void* w16 /*or NULL*/, int w16_dtype, int64_t begin,
+                             int64_t end, const d2r_adamw_seg* d_table, int nseg, int64_t n, const float* d_hyper, int ngroups,
+                             float beta1, float beta2, float eps, const int* d_skip /*or NULL*/, const float* d_coef /*or NULL*/,
+                             float* ema /*or NULL*/, const float* d_ema_one_minus_decay /*or NULL without ema*/, void* stream);
 /* a[i] <-> b[i] for i < n in one pass (16-byte vector path when both pointers are 16-byte aligned, scalar otherwise); the ranges
  * must not overlap; n == 0 launches nothing.  Evaluation on the averaged weights swaps them in and out with this. */
 int d2r_swap_f32(float* a, float* b, int64_t n, void* stream);
