@@ -47,7 +47,7 @@ class EncoderLayerDesc(C.Structure):
                                      "mean1", "rstd1", "mean2", "rstd2", "dy", "dx", "scratch")]
                 + [("scratch_bytes", sz), ("splitk_ws", vp), ("splitk_bytes", sz), ("wgrad_stream", vp),
                    ("defer_wgrad", i32), ("o_dy", vp * 4), ("defer_ln", i32), ("o_lnws", vp * 2), ("p_attn", f32), ("p_hidden", f32), ("seed_attn", C.c_uint64),
-                   ("seed_hidden", C.c_uint64 * 2)])
+                   ("seed_hidden", C.c_uint64 * 2), ("p_path", f32), ("seed_path", C.c_uint64 * 2)])
 
 
 RL_NAMES = ("R0", "R2", "IMRC_QKV", "IMRC_FC1", "IMRC_FC2", "GLAC_Q", "GLAC_KV", "GLAC_LOC", "GLAC_FC1", "GLAC_TPOOL", "GLAC_IPOOL",
@@ -164,6 +164,7 @@ SIGNATURES = {
     "d2r_add2": (i32, [i32, vp, vp, vp, vp, vp, vp, i64, vp]),
     "d2r_act_bwd2": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
     "d2r_dropout": (i32, [i32, vp, vp, vp, i64, f32, C.c_uint64, vp]),
+    "d2r_drop_path": (i32, [i32, vp, vp, vp, i64, i64, f32, C.c_uint64, f32, C.c_uint64, vp]),
     "d2r_lincomb": (i32, [C.POINTER(vp), C.POINTER(f32), i32, vp, vp]),
     "d2r_axpby": (i32, [i32, f32, vp, f32, vp, i64, vp]),
     "d2r_cast": (i32, [i32, vp, i32, vp, i64, vp]),

@@ -236,6 +236,84 @@ extern "C" int d2r_dropout(int dtype, const void* x, const void* add, void* y, i
   return d2r_check_launch("d2r_dropout");
 }
 
+// ---- stochastic depth (DropPath) ---------------------------------------------------------------------------
+// y = add + keep_path(b) / (1 - p_path) * dropout_elem(x) over [B, per_sample]: the residual branch of sample b is dropped whole
+// when d2r_rand24(seed_path, b) falls below the threshold (an extension: the reference has no DropPath).  The sample rides on
+// blockIdx.y, so the decision is taken once per block and sample, is uniform over the wave, and costs no division per element.
+// A dropped sample is a select: its rows become a bit copy of `add` (+0 without it) and its x is never read.  A kept element
+// is d2r_dropout's value times 1/(1 - p_path), in the same order of fp32 operations on the vector and the scalar path (no FMA
+// contraction: both paths, and the composite layer and the op-by-op path, must agree bit for bit).  x and y may be one buffer.
+template <typename T>
+__device__ __forceinline__ T drop_path_value(T x, bool keep, float scale_elem, float scale_path, bool has_add, T add) {
+#pragma clang fp contract(off)
+  float v = keep ? to_f<T>(x) * scale_elem : 0.f;
+  v = v * scale_path;
+  if (has_add) v = v + to_f<T>(add);
+  return from_f<T>(v);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void drop_path_kernel(const T* x, const T* add, T* y, int64_t B, int64_t per_sample, uint32_t thresh_path,
+                                                        float scale_path, uint64_t seed_path, uint32_t thresh_elem, float scale_elem,
+                                                        uint64_t seed_elem, int vec_ok) {
+  constexpr int VEC = PackOf<T>::N;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  const int64_t npk = vec_ok ? per_sample / VEC : 0;  // vec_ok: per_sample is a multiple of VEC, every sample starts on 16 bytes
+  for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
+    const int64_t base = b * per_sample;
+    const T* xb = x + base;
+    const T* ab = add ? add + base : nullptr;
+    T* yb = y + base;
+    if (d2r_rand24(seed_path, (uint64_t)b) < thresh_path) {  // dropped: copy the skip connection, never touch x
+      Pack<T, VEC> zero;
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) zero.v[j] = from_f<T>(0.f);
+      for (int64_t k = tid; k < npk; k += nthreads) st_pack<T, VEC>(yb + k * VEC, ab ? ld_pack<T, VEC>(ab + k * VEC) : zero);
+      for (int64_t e = npk * VEC + tid; e < per_sample; e += nthreads) yb[e] = ab ? ab[e] : zero.v[0];
+      continue;
+    }
+    for (int64_t k = tid; k < npk; k += nthreads) {
+      const Pack<T, VEC> px = ld_pack<T, VEC>(xb + k * VEC);
+      Pack<T, VEC> pa = px, po;
+      if (ab) pa = ld_pack<T, VEC>(ab + k * VEC);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const bool keep = d2r_rand24(seed_elem, (uint64_t)(base + k * VEC + j)) >= thresh_elem;
+        po.v[j] = drop_path_value<T>(px.v[j], keep, scale_elem, scale_path, ab != nullptr, pa.v[j]);
+      }
+      st_pack<T, VEC>(yb + k * VEC, po);
+    }
+    for (int64_t e = npk * VEC + tid; e < per_sample; e += nthreads) {
+      const bool keep = d2r_rand24(seed_elem, (uint64_t)(base + e)) >= thresh_elem;
+      yb[e] = drop_path_value<T>(xb[e], keep, scale_elem, scale_path, ab != nullptr, ab ? ab[e] : xb[e]);
+    }
+  }
+}
+
+extern "C" int d2r_drop_path(int dtype, const void* x, const void* add, void* y, int64_t B, int64_t per_sample, float p_path,
+                             uint64_t seed_path, float p_elem, uint64_t seed_elem, void* stream) {
+  D2R_REQUIRE(x && y && B >= 0 && per_sample >= 0, "d2r_drop_path: bad arguments (null x or y, or a negative size)");
+  D2R_REQUIRE(p_path >= 0.f && p_path < 1.f && p_elem >= 0.f && p_elem < 1.f, "d2r_drop_path: probabilities must be in [0, 1)");
+  D2R_REQUIRE(dtype == D2R_BF16 || dtype == D2R_F16 || dtype == D2R_F32, "d2r_drop_path: bad dtype %d", dtype);
+  if (B == 0 || per_sample == 0) return D2R_OK;
+  D2R_REQUIRE(per_sample <= INT64_MAX / B, "d2r_drop_path: B * per_sample overflows");
+  if (p_path == 0.f) return d2r_dropout(dtype, x, add, y, B * per_sample, p_elem, seed_elem, stream);  // no path mask: bit for bit d2r_dropout
+  const int VEC = dtype != D2R_F32 ? 8 : 4;
+  const int vec_ok = d2r_aligned16(x) && d2r_aligned16(y) && d2r_aligned16(add) && per_sample % VEC == 0;
+  const uint32_t thresh_path = d2r_drop_threshold(p_path), thresh_elem = d2r_drop_threshold(p_elem);
+  const float scale_path = 1.f / (1.f - p_path), scale_elem = 1.f / (1.f - p_elem);
+  const int gy = (int)(B < 65535 ? B : 65535);  // the sample on blockIdx.y (strided beyond the grid limit)
+  const int64_t need = (per_sample / VEC + 1 + 255) / 256;
+  const int64_t cap = 2048 / gy > 0 ? 2048 / gy : 1;  // ~256 CUs x 8 blocks in all, grid-stride inside the sample for the rest
+  const dim3 grid((unsigned)(need < cap ? need : cap), (unsigned)gy);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == D2R_BF16) hipLaunchKernelGGL((drop_path_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)add, (bf16_t*)y, B, per_sample, thresh_path, scale_path, seed_path, thresh_elem, scale_elem, seed_elem, vec_ok);
+  else if (dtype == D2R_F16) hipLaunchKernelGGL((drop_path_kernel<f16_t>), grid, dim3(256), 0, st, (const f16_t*)x, (const f16_t*)add, (f16_t*)y, B, per_sample, thresh_path, scale_path, seed_path, thresh_elem, scale_elem, seed_elem, vec_ok);
+  else hipLaunchKernelGGL((drop_path_kernel<float>), grid, dim3(256), 0, st, (const float*)x, (const float*)add, (float*)y, B, per_sample, thresh_path, scale_path, seed_path, thresh_elem, scale_elem, seed_elem, vec_ok);
+  return d2r_check_launch("d2r_drop_path");
+}
+
 // out[0] = sum_k coef[k] * x_k[0]  (scalar loss combination: CE + js terms, models/unimo_model.py:160,
 // models/modeling_unimo.py:849)
 struct LinCombArgs {

@@ -963,7 +963,7 @@ def _layer_scratch(nbytes: int, device) -> torch.Tensor:
 
 class _EncoderLayer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, anchor, bundle, mask, p_attn, p_hidden):
+    def forward(ctx, x, anchor, bundle, mask, p_attn, p_hidden, p_path=0.0):
         x = x.contiguous()
         B, L, E = x.shape
         T, Fi, H = B * L, bundle.F, bundle.H
@@ -979,6 +979,11 @@ class _EncoderLayer(torch.autograd.Function):
         if p_hidden > 0.0:
             d.seed_hidden[0] = _next_dropout_seed()
             d.seed_hidden[1] = _next_dropout_seed()
+        # stochastic depth: a seed per residual branch (attention, then FFN) from DropPath's own generator, as drop_path draws them
+        d.p_path = p_path
+        if p_path > 0.0:
+            d.seed_path[0] = _next_drop_path_seed()
+            d.seed_path[1] = _next_drop_path_seed()
         acts = torch.empty(T * (7 * E + 2 * Fi), dtype=x.dtype, device=x.device)  # qkv ctx h1 n1 h2 | f_pre f
         stats = torch.empty(B * H * L + 4 * T, dtype=torch.float32, device=x.device)
         y = torch.empty_like(x)
@@ -1050,13 +1055,16 @@ class _EncoderLayer(torch.autograd.Function):
             cb = getattr(p, "_d2r_ready_cb", None)
             if cb is not None:
                 cb(p)
-        return dx, None, None, None, None, None
+        return dx, None, None, None, None, None, None
 
 
-def encoder_layer(x, bundle: LayerBundle, mask=None, p_attn: float = 0.0, p_hidden: float = 0.0):
+def encoder_layer(x, bundle: LayerBundle, mask=None, p_attn: float = 0.0, p_hidden: float = 0.0, p_path: float = 0.0):
     """One whole BertLayer / CLIPEncoderLayer (16-bit compute dtype) as a single autograd node and a single C call each way;
-    p_attn / p_hidden: training-time dropout on the attention probabilities / on the two dense outputs."""
-    return _EncoderLayer.apply(x, bundle.params[0], bundle, mask, float(p_attn), float(p_hidden))
+    p_attn / p_hidden: training-time dropout on the attention probabilities / on the two dense outputs; p_path: training-time
+    stochastic depth of the two residual branches (drop_path)."""
+    if not 0.0 <= p_path < 1.0:
+        raise ValueError(f"drop_path probability {p_path} outside [0, 1)")
+    return _EncoderLayer.apply(x, bundle.params[0], bundle, mask, float(p_attn), float(p_hidden), float(p_path))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1555,6 +1563,74 @@ def dropout(x, p: float, training: bool, residual=None):
     if not 0.0 <= p < 1.0:
         raise ValueError(f"dropout probability {p} outside [0, 1)")
     return _Dropout.apply(x, residual, float(p), _next_dropout_seed())
+
+
+# Stochastic depth (DropPath; an extension, the reference has none): the residual branch of a sample is dropped whole with
+# probability p and scaled by 1 / (1 - p) otherwise.  The mask is a pure function of (seed, sample index); the seeds come from a CPU
+# generator of DropPath's own, so torch's default generator (the samplers, the dropout seeds) is never touched and every other
+# random choice of a run stays what it was (as d2r_amd.augment does for its boxes).
+_DROP_PATH_TAG = 0x64726F7070617468  # "droppath": keeps the stream apart from the augmenter's and from a default generator
+_drop_path_generator = None
+
+
+def drop_path_stream_seed(seed: int, rank: int = 0) -> int:
+    """The seed of rank `rank`'s DropPath generator in a run seeded `seed`: augment.stream_seed's construction with DropPath's tag,
+    ``(((seed mod 2^32) << 24) | rank) ^ tag`` reduced mod 2^64: distinct (seed mod 2^32, rank) pairs give distinct seeds."""
+    if not 0 <= int(rank) < (1 << 24):
+        raise ValueError(f"rank must be in [0, 2^24), got {rank}")
+    return ((((int(seed) & 0xFFFFFFFF) << 24) | int(rank)) ^ _DROP_PATH_TAG) & 0xFFFFFFFFFFFFFFFF
+
+
+def seed_drop_path(seed: int, rank: int = 0):
+    """(Re)seeds DropPath's generator for rank `rank` of a run seeded `seed`; the ranks of a data-parallel run get different streams."""
+    global _drop_path_generator
+    if _drop_path_generator is None:
+        _drop_path_generator = torch.Generator(device="cpu")
+    _drop_path_generator.manual_seed(drop_path_stream_seed(seed, rank))
+
+
+def _next_drop_path_seed() -> int:
+    if _drop_path_generator is None:  # never seeded: from torch's initial seed (read, not drawn from) and rank 0
+        seed_drop_path(torch.initial_seed(), 0)
+    return int(torch.empty((), dtype=torch.int64).random_(generator=_drop_path_generator).item())
+
+
+class _DropPath(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, residual, p, seed, p_elem, seed_elem):
+        x = x.contiguous()
+        if residual is not None:
+            residual = residual.contiguous()
+            assert residual.shape == x.shape and residual.dtype == x.dtype
+        y = torch.empty_like(x)
+        B = x.shape[0]
+        per_sample = x.numel() // B if B else 0
+        _lib.call("d2r_drop_path", _dt(x), x.data_ptr(), _ptr(residual), y.data_ptr(), B, per_sample, p, seed, p_elem, seed_elem,
+                  _stream())
+        ctx.cfg = (B, per_sample, p, seed, p_elem, seed_elem, residual is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        B, per_sample, p, seed, p_elem, seed_elem, has_res = ctx.cfg
+        g = g.contiguous()
+        dx = torch.empty_like(g)
+        _lib.call("d2r_drop_path", _dt(g), g.data_ptr(), None, dx.data_ptr(), B, per_sample, p, seed, p_elem, seed_elem, _stream())
+        return dx, (g if has_res else None), None, None, None, None
+
+
+def drop_path(x, p: float, training: bool, residual=None, p_elem: float = 0.0):
+    """Stochastic depth of a residual branch x [B, ...] (+ residual): sample b is dropped whole with probability p, else scaled by
+    1 / (1 - p); the per-sample size is x[0].numel().  p_elem > 0 applies nn.Dropout(p_elem) to x in the same pass (its seed comes
+    from the default generator, as dropout's does, and is drawn first).  Not training or p == 0: dropout(x, p_elem, training, residual)."""
+    if not training or p <= 0.0:
+        return dropout(x, p_elem, training, residual)
+    if not (0.0 <= p < 1.0 and 0.0 <= p_elem < 1.0):
+        raise ValueError(f"drop_path probabilities {p}, {p_elem} outside [0, 1)")
+    if x.dim() < 1:
+        raise ValueError("drop_path needs a batch dimension")
+    seed_elem = _next_dropout_seed() if p_elem > 0.0 else 0
+    return _DropPath.apply(x, residual, float(p), _next_drop_path_seed(), float(p_elem), seed_elem)
 
 
 class _LinComb(torch.autograd.Function):

@@ -568,6 +568,17 @@ COMPOSITE_HEAD = True  # Block fusion + fc + cross entropy + loss as one C call 
 COMPOSITE_ROUTING = True  # whole interaction modules as one C call (bf16 only)
 
 
+def drop_path_schedule(rate: float, num_layers: int):
+    """Stochastic-depth probabilities of the `num_layers` encoder layers of one tower, growing linearly with depth from 0 to `rate`
+    (timm's / BEiT's ``linspace(0, rate, L)``): layer i (0-based) gets rate * i / (L - 1); a single layer gets 0."""
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"drop_path rate must be in [0, 1), got {rate}")
+    if num_layers < 0:
+        raise ValueError(f"num_layers must be >= 0, got {num_layers}")
+    return [rate * i / (num_layers - 1) if num_layers > 1 else 0.0 for i in range(num_layers)]
+
+
 def _layer_bundle(layer, x):
     """The cached LayerBundle of a BertLayer / CLIPEncoderLayer when the one-call path applies (bf16 model prepared by
     ParamStore, fused q|k|v, attention shape supported by the fused core), else None -> the op-by-op path."""
@@ -634,6 +645,7 @@ class BertLayer(D2RModule):
         self.intermediate = BertIntermediate(config)
         self.output = BertOutput(config)
         self.p_hidden = config.hidden_dropout_prob
+        self.p_path = 0.0  # stochastic depth of the two residual branches, training only (UnimoModel.set_drop_path)
 
     def _bundle(self):
         sa, so = self.attention.self, self.attention.output
@@ -651,9 +663,10 @@ class BertLayer(D2RModule):
         # probabilities are masked inside the fused attention core, the two dense outputs by one in-place pass each
         p_att = sa.p_drop if self.training else 0.0
         p_hid = self.p_hidden if self.training else 0.0
+        p_path = self.p_path if self.training else 0.0
         bundle = _layer_bundle(self, x)
         if bundle is not None:
-            return F.encoder_layer(x, bundle, key_mask, p_att, p_hid)
+            return F.encoder_layer(x, bundle, key_mask, p_att, p_hid, p_path)
         H = sa.num_attention_heads
         scale = 1.0 / math.sqrt(x.shape[-1] // H)
         fz = sa._fused_linear()
@@ -661,6 +674,10 @@ class BertLayer(D2RModule):
             ctx = F.attention_qkv(fz(x, self.cdtype), H, scale, mask=key_mask, p_drop=p_att)
         else:
             ctx = F.attention(sa.query(x), sa.key(x), sa.value(x), H, scale, mask=key_mask, p_drop=p_att)
+        if p_path > 0.0:  # stochastic depth: the per-sample mask, the dropout and the skip connection in one pass
+            a = self.attention.output.LayerNorm(F.drop_path(self.attention.output.dense(ctx), p_path, True, residual=x, p_elem=p_hid))
+            h = self.intermediate.dense(a, act=ACT_GELU)
+            return self.output.LayerNorm(F.drop_path(self.output.dense(h), p_path, True, residual=a, p_elem=p_hid))
         if p_hid > 0.0:
             a = self.attention.output.LayerNorm(F.dropout(self.attention.output.dense(ctx), p_hid, True, residual=x))
             h = self.intermediate.dense(a, act=ACT_GELU)
@@ -700,6 +717,7 @@ class CLIPEncoderLayer(D2RModule):
         self.layer_norm1 = LayerNorm(config.hidden_size, eps=1e-5)  # the reference builds nn.LayerNorm(dim): eps 1e-5
         self.mlp = CLIPMLP(config)
         self.layer_norm2 = LayerNorm(config.hidden_size, eps=1e-5)
+        self.p_path = 0.0  # stochastic depth of the two residual branches, training only (UnimoModel.set_drop_path)
 
     def _bundle(self):
         at = self.self_attn
@@ -713,9 +731,10 @@ class CLIPEncoderLayer(D2RModule):
     def forward(self, x):
         at = self.self_attn
         p_att = at.p_drop if self.training else 0.0  # attention_dropout (models/modeling_unimo.py:204), 0 by default
+        p_path = self.p_path if self.training else 0.0
         bundle = _layer_bundle(self, x)
         if bundle is not None:
-            return F.encoder_layer(x, bundle, None, p_att, 0.0)
+            return F.encoder_layer(x, bundle, None, p_att, 0.0, p_path)
         h = self.layer_norm1(x)
         d = x.shape[-1] // at.num_heads
         fz = at._fused_linear()
@@ -723,6 +742,10 @@ class CLIPEncoderLayer(D2RModule):
             ctx = F.attention_qkv(fz(h, self.cdtype), at.num_heads, d ** -0.5, p_drop=p_att)
         else:
             ctx = F.attention(at.q_proj(h), at.k_proj(h), at.v_proj(h), at.num_heads, d ** -0.5, p_drop=p_att)
+        if p_path > 0.0:
+            x = F.drop_path(at.out_proj(ctx), p_path, True, residual=x)
+            h = self.mlp.fc1(self.layer_norm2(x), act=ACT_QUICK_GELU)
+            return F.drop_path(self.mlp.fc2(h), p_path, True, residual=x)
         x = at.out_proj(ctx, residual=x)
         h = self.mlp.fc1(self.layer_norm2(x), act=ACT_QUICK_GELU)
         return self.mlp.fc2(h, residual=x)
@@ -857,6 +880,16 @@ class UnimoModel(D2RModule):
         self.text_pooler = BertPooler() if add_pooling_layer else None  # dead (ingest assert needs it)
         self.use_streams = os.environ.get("D2R_STREAMS", "1") != "0"
         self._streams = None
+
+    def set_drop_path(self, rate: float):
+        """Stochastic depth (an extension, off by default): layer i of each encoder tower gets drop_path_schedule(rate, L)[i], used
+        in train() mode only; the self layers and the interaction modules stay at 0.  Returns (text rates, vision rates)."""
+        towers = (self.encoder.text_layer, self.encoder.vision_layers)
+        rates = tuple(drop_path_schedule(rate, len(t)) for t in towers)
+        for layers, rs in zip(towers, rates):
+            for layer, r in zip(layers, rs):
+                layer.p_path = r
+        return rates
 
     def _head_bundle(self, fc):
         """The cached HeadBundle when the one-call head applies (fp32 parameters with gradient sinks, the 20 + 20 merge groups

@@ -16,6 +16,7 @@ allowed), --write_path writes the per-sample predictions as JSON Lines (MSDTrain
 --label_smoothing E / --class_weights {none | balanced | W0,W1,...} are the options of the cross entropy (inside its kernels).
 --aug_crop_scale LO / --aug_flip P (with --data_path) augment the training images on the device (d2r_amd.augment).
 --layer_lr_decay D / --wd_exempt_1d / --weight_decay W: AdamW hyper-parameters per parameter, still one launch (d2r_adamw_step_table).
+--drop_path P: stochastic depth of the two encoder towers, growing linearly with depth from 0 to P (d2r_drop_path), training only.
 """
 from __future__ import annotations
 
@@ -87,6 +88,13 @@ def _aug_flip(text):
     v = float(text)
     if not 0 <= v <= 1:
         raise argparse.ArgumentTypeError(f"must be in [0, 1] (0 = no flipping), got {text}")
+    return v
+
+
+def _drop_path(text):
+    v = float(text)
+    if not 0 <= v < 1:
+        raise argparse.ArgumentTypeError(f"must be in [0, 1) (0 = off), got {text}")
     return v
 
 
@@ -200,6 +208,10 @@ def build_parser():
                    "LayerNorm / BatchNorm weight and bias, CLIP's class embedding (off = the reference's behaviour)")
     p.add_argument("--weight_decay", default=1e-2, type=_weight_decay, help="AdamW's decoupled weight decay, finite and >= 0 "
                    "(1e-2 = the reference's)")
+    p.add_argument("--drop_path", default=0.0, type=_drop_path, help="stochastic depth (DropPath) of the two pretrained towers: in "
+                   "training, encoder layer i of L drops each of its two residual branches per sample with probability P * i / (L - 1) "
+                   "and scales it by the inverse of the rest otherwise (timm's / BEiT's linear schedule); in [0, 1), 0 = off, the "
+                   "reference's behaviour; dev, test and prediction passes are never affected")
     p.add_argument("--label_smoothing", default=0.0, type=_label_smoothing, help="label smoothing of the cross entropy, in [0, 1), as "
                    "torch.nn.CrossEntropyLoss(label_smoothing=) (0 = off, the reference's behaviour); training, dev and test loss alike")
     p.add_argument("--class_weights", default="none", type=str, help="per-class weights of the cross entropy, as "
@@ -357,6 +369,9 @@ def main(argv=None):
     if args.only_test and (args.layer_lr_decay != 1.0 or args.wd_exempt_1d or args.weight_decay != 1e-2):
         logger.info("--layer_lr_decay / --wd_exempt_1d / --weight_decay are ignored with --only_test: no optimiser step is taken")
         args.layer_lr_decay, args.wd_exempt_1d, args.weight_decay = 1.0, False, 1e-2
+    if args.only_test and args.drop_path:
+        logger.info("--drop_path is ignored with --only_test: stochastic depth acts on training steps only")
+        args.drop_path = 0.0
     if class_weights == "balanced":
         try:
             class_weights = balanced_class_weights(train_label_counts(args, None if args.data_path is None else files[0]))

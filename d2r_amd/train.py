@@ -11,7 +11,8 @@ state-dict key names (:210-216).  Differences, all deliberate (SURVEY.md Appendi
   * optional data parallelism (args.world_size > 1 via torch.distributed, see d2r_amd.dp);
   * optional extensions: gradient clipping (args.max_grad_norm) and a weight EMA (args.ema_decay: evaluate() / test() run on
     the averaged weights and best_model.pth holds them; BatchNorm running statistics stay the live ones), layer-wise lr decay and
-    no weight decay on 1-D parameters (args.layer_lr_decay, args.wd_exempt_1d), the weight decay itself (args.weight_decay);
+    no weight decay on 1-D parameters (args.layer_lr_decay, args.wd_exempt_1d), the weight decay itself (args.weight_decay),
+    stochastic depth of the two encoder towers in training steps (args.drop_path; its seeds come from a generator of its own);
   * optional image augmentation of the TRAINING batches (``augmenter``, d2r_amd.augment: random resized crop and flip on the
     device; a CachedLoader carries its own); evaluate() / test() / predict() never augment;
   * evaluate() / test() count a confusion matrix on the device (d2r_confusion_add) instead of copying labels and predictions to
@@ -174,6 +175,13 @@ class MSDTrainer:
                                shard_optimizer=shard, algorithm=getattr(self.args, "dp_algorithm", "all_reduce"),
                                global_batch_exact=bool(getattr(self.args, "dp_exact", False)))
         self.dp.broadcast_parameters()
+        # stochastic depth: per-layer rates on the two towers, and DropPath's own generator seeded from (seed, rank) - the default
+        # generator is not drawn from.  Off (0) leaves the model as it was built.
+        self.drop_path_rates = None
+        rate = float(getattr(self.args, "drop_path", 0.0) or 0.0)
+        if rate > 0.0 and self.train_data is not None:
+            self.drop_path_rates = self.model.model.set_drop_path(rate)
+            F.seed_drop_path(int(getattr(self.args, "seed", 0)), self.dp.rank)
         if self.train_data is not None:
             self.scheduler = LinearWarmupSchedule(self.optimizer, self.args.warmup_ratio * self.train_num_steps,
                                                   self.train_num_steps)
@@ -217,6 +225,9 @@ class MSDTrainer:
                              "smallest lr scale: text tower %g, vision tower %g", len(self.optimizer.table),
                              self.optimizer.layer_lr_decay, self.optimizer.param_groups[0]["weight_decay"],
                              ", none on 1-D parameters" if self.optimizer.decay_exempt_1d else "", *self.optimizer.tower_lr_scales)
+        if self.drop_path_rates is not None:
+            self.logger.info("  Stochastic depth (training steps only): drop_path per layer, text tower [%s], vision tower [%s]",
+                             *(", ".join(f"{r:.4g}" for r in rs) for rs in self.drop_path_rates))
         augmenter = self.augmenter or getattr(self.train_data, "augmenter", None)
         if augmenter is not None:
             self.logger.info("  Image augmentation of the training batches: %s", augmenter.describe())

@@ -184,6 +184,19 @@ int d2r_lerp_bwd(int dtype, const void* g, const void* a, const void* b, const v
  * (the skip connection that follows the dropout in BertSelfOutput / BertOutput).  keep(i) is a pure function of
  * (seed, i): the backward pass calls the same entry point on dy with the same seed — no mask is stored. */
 int d2r_dropout(int dtype, const void* x, const void* add, void* y, int64_t n, float p, uint64_t seed, void* stream);
+/* Stochastic depth (DropPath; an extension, the reference has none) fused with the dropout above and the skip connection, over
+ * x [B, per_sample] (bf16, fp16 or fp32; y == x allowed):
+ *   y = add + keep_path(b) / (1 - p_path) * dropout_elem(x),  b = i / per_sample,  i in [0, B * per_sample)
+ * dropout_elem is d2r_dropout's element mask with (p_elem, seed_elem) at element index i (p_elem = 0: identity).
+ * keep_path(b) = rand24(seed_path, b) >= p_path * 2^24, the same counter-based generator applied to the SAMPLE index: a pure function
+ * of (seed_path, b).  The backward pass calls the same entry point on dy with add = NULL and the same seeds.
+ * A dropped sample is a select, not a multiply: its rows of y are a bit copy of add (+0 without add) and its x is never read, so an
+ * inf / NaN in a dropped branch does not reach y.  A kept element is ((keep_elem ? x / (1 - p_elem) : 0) / (1 - p_path)) + add in
+ * fp32, rounded once to the dtype; p_path = 0 is bit for bit d2r_dropout.  p_path, p_elem outside [0, 1): D2R_ERR_INVALID, no
+ * launch.  B == 0 or per_sample == 0: no-op.  16-byte packs when x, add, y are 16-byte aligned and per_sample is a multiple of the
+ * pack width (8 / 4 elements), else element by element; both keep exactly the same elements. */
+int d2r_drop_path(int dtype, const void* x, const void* add, void* y, int64_t B, int64_t per_sample, float p_path,
+                  uint64_t seed_path, float p_elem, uint64_t seed_elem, void* stream);
 int d2r_add(int dtype, const void* a, const void* b, void* out, int64_t n, void* stream);
 /* two independent problems of one size in one launch (element for element the arithmetic of two d2r_add / d2r_act_bwd calls): the
  * text / image and a / b pairs of per-sample vectors in the routing cells' backward (models/Cells.py:179-218, :222-255) */
@@ -455,6 +468,12 @@ typedef struct {
    * call regenerates them from the same values. */
   float p_attn, p_hidden;
   uint64_t seed_attn, seed_hidden[2];
+  /* training-time stochastic depth (an extension; 0 = off, what a zero-initialised tail means): each of the two residual branches
+   * is dropped per sample with probability p_path and scaled by 1 / (1 - p_path) otherwise, by the pass that applies p_hidden
+   * (d2r_drop_path over [B, L*E]; p_path = 0 leaves the call sequence as it was).  seed_path[0]: attention branch, [1]: FFN
+   * branch; the mask is a function of (seed, sample index) and the backward call regenerates it. */
+  float p_path;
+  uint64_t seed_path[2];
 } d2r_encoder_layer_desc;
 size_t d2r_encoder_layer_bwd_scratch(int B, int L, int E, int F);
 int d2r_encoder_layer_fwd(const d2r_encoder_layer_desc* d, void* stream);
