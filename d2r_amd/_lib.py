@@ -92,6 +92,11 @@ class ClipAugmentDesc(C.Structure):
     _fields_ = [(n, i32) for n in ("x0", "y0", "w", "h", "flip")] + [("reserved", i32 * 3)]
 
 
+class ClipPhotoDesc(C.Structure):  # d2r_clip_photo_desc, 48 bytes
+    _fields_ = [(n, f32) for n in ("brightness", "contrast", "saturation", "hue")] + \
+        [(n, i32) for n in ("gray", "ex0", "ey0", "ew", "eh")] + [("reserved", i32 * 3)]
+
+
 class JpegImageDesc(C.Structure):
     _fields_ = [(n, i64) for n in ("dst_offset", "ws_rec", "ws_coef", "ws_plane")] + \
         [(n, i32) for n in ("H", "W", "ncomp", "hs", "vs", "fancy", "mcux", "mcuy", "mcu_blocks", "restart", "seg0", "nseg", "nchunk")] + \
@@ -205,6 +210,9 @@ SIGNATURES = {
     "d2r_clip_cache_gather": (i32, [vp, i64, vp, vp, i32, i32, vp, vp, vp]),
     "d2r_gather_rows": (i32, [vp, vp, i64, i64, vp, vp, i32, vp]),
     "d2r_clip_cache_augment": (i32, [vp, i64, vp, vp, C.POINTER(ClipAugmentDesc), vp, i32, i32, vp, vp, vp]),
+    "d2r_clip_cache_augment_photo_ws_bytes": (sz, [i32, i32]),
+    "d2r_clip_cache_augment_photo": (i32, [vp, i64, vp, vp, C.POINTER(ClipAugmentDesc), vp, C.POINTER(ClipPhotoDesc), vp, i32, i32,
+                                           C.POINTER(f32), f32, vp, vp, sz, vp]),
     "d2r_jpeg_decode_ws_bytes": (sz, [C.POINTER(JpegImageDesc), i32]),
     "d2r_jpeg_decode": (i32, [vp, i64, C.POINTER(JpegImageDesc), vp, i32, C.POINTER(JpegSegment), vp, i32, vp, vp, i64,
                               vp, i64, vp, vp, vp, sz, vp]),

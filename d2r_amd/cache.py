@@ -18,7 +18,9 @@ found it: the dropout seeds come from it (functional._next_dropout_seed), so a r
 without.
 
 The cache holds the un-augmented crops.  A training loader may carry an ``Augmenter`` (d2r_amd.augment, --aug_crop_scale /
---aug_flip): its batches' pixel values then come from d2r_clip_cache_augment, the same launch with a box and a flip per sample.
+--aug_flip): its batches' pixel values then come from d2r_clip_cache_augment, the same launch with a box and a flip per sample -
+or, with a photometric option on (--aug_brightness / --aug_contrast / --aug_saturation / --aug_hue / --aug_grayscale / --aug_erase),
+from d2r_clip_cache_augment_photo, which also jitters the colours, greys and erases per sample.
 """
 from __future__ import annotations
 
@@ -104,6 +106,7 @@ class DeviceDatasetCache:
         self.input_ids, self.input_mask, self.segment_ids = (torch.empty(n, max_seq, dtype=torch.int64, device=self.device)
                                                              for _ in range(3))
         self.labels = torch.empty(n, dtype=torch.int64, device=self.device)
+        self.norm = norm
         self.lut = I._device_table(str(self.device), norm)
         self.img_mask = None      # the constant row, [ntok] on the device, from the first batch
         self._h_img_mask = None
@@ -158,6 +161,8 @@ class DeviceDatasetCache:
         if augmenter is None:
             images = I.clip_cache_gather(self.crops, h_idx, idx, self.S, self.lut)
         else:
+            if augmenter.photometric and augmenter.norm != self.norm:  # the photometric kernel normalises by value, not by the table
+                raise ValueError(f"the {self.split} cache is normalised with {self.norm}, the augmenter was built with {augmenter.norm}")
             images = augmenter.apply(self.crops, h_idx, idx, self.lut)
         batch = CachedBatch((I.gather_rows(self.input_ids, h_idx, idx), I.gather_rows(self.input_mask, h_idx, idx),
                              I.gather_rows(self.segment_ids, h_idx, idx), self.img_mask.expand(h_idx.numel(), -1),

@@ -12,9 +12,12 @@
 // planar [3, S, S], into a row of a device-resident cache, and d2r_clip_cache_gather maps rows picked by index through the table
 // into the fp32 batch.  d2r_gather_rows does the same row pick for the token tensors.  d2r_clip_cache_augment is the gather with
 // a per-sample box of the crop resampled bilinearly to S x S and an optional mirror (d2r_amd/augment.py: random resized crop, flip).
+// d2r_clip_cache_augment_photo resamples the raw values instead of the table's and applies brightness, contrast, saturation, hue,
+// grayscale, the normalisation and an erase box per sample (K22: colour jitter, random grayscale, random erasing).
 #include "common.h"
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 namespace {
@@ -200,6 +203,162 @@ __global__ __launch_bounds__(256) void clip_cache_augment_kernel(const uint8_t* 
   }
 }
 
+// ---- K22: photometric augmentation (colour jitter, grayscale, erasing) of the resampled box, before the normalisation ----
+
+constexpr int PHOTO_BLOCK = 256;  // threads per workgroup of both K22 kernels = pixels quads per partial sum of the statistics pass
+
+__device__ __forceinline__ float photo_clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }  // a NaN becomes 0
+
+// g(x) = 0.299 R + 0.587 G + 0.114 B, summed left to right
+__device__ __forceinline__ float photo_gray(float r, float g, float b) { return 0.299f * r + 0.587f * g + 0.114f * b; }
+
+// K21's resample (aug_axis / aug_blend, the same taps) of the raw values P * rescale for columns j0 .. j0 + 3 of output row i, all
+// three channels; `row` is the sample's cache row.  Columns past the row are computed again from column S - 1.
+__device__ __forceinline__ void photo_resample(const uint8_t* __restrict__ row, const d2r_clip_augment_desc& d, int flip, int i, int j0,
+                                               int S, float rescale, float x[3][4]) {
+  const int plane = S * S;
+  const aug_tap ty = aug_axis(i, d.h, S);
+  const uint8_t* r0 = row + d.x0 + (d.y0 + ty.lo) * S;
+  const uint8_t* r1 = row + d.x0 + (d.y0 + ty.hi) * S;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int j = min(j0 + k, S - 1);
+    const aug_tap tx = aug_axis(flip ? S - 1 - j : j, d.w, S);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const uint8_t* p0 = r0 + c * plane;
+      const uint8_t* p1 = r1 + c * plane;
+      x[c][k] = aug_blend((float)p0[tx.lo] * rescale, (float)p0[tx.hi] * rescale, (float)p1[tx.lo] * rescale, (float)p1[tx.hi] * rescale,
+                          tx.f, ty.f);
+    }
+  }
+}
+
+// step 1 (skipped by the caller when beta == 1)
+__device__ __forceinline__ float photo_brightness(float x, float beta) { return photo_clamp01(beta * x); }
+
+// step 4: RGB -> HSV (hexcone; h = 0 when max == min, s = 0 when max == 0), h <- frac(h + delta), HSV -> RGB
+__device__ __forceinline__ void photo_hue(float& r, float& g, float& b, float delta) {
+  const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b));
+  const float cr = mx - mn;
+  const bool grey = cr == 0.0f;
+  const float s = cr / (grey ? 1.0f : mx);  // mx > 0 when cr > 0
+  const float inv = 1.0f / (grey ? 1.0f : cr);
+  const float rc = (mx - r) * inv, gc = (mx - g) * inv, bc = (mx - b) * inv;
+  const float h6 = mx == r ? bc - gc : (mx == g ? 2.0f + rc - bc : 4.0f + gc - rc);  // in [-1, 5]
+  float h = h6 * (1.0f / 6.0f) + delta;                                              // in (-0.67, 1.34)
+  h = h - floorf(h);                                                                 // in [0, 1]; 1 when h was a tiny negative
+  const float hs = h * 6.0f, fl = floorf(hs), f = hs - fl;
+  int sec = (int)fl;
+  if (sec >= 6) sec -= 6;  // hs == 6 has f == 0, where sector 0 gives what sector 5 gives at f == 1
+  const float p = photo_clamp01(mx * (1.0f - s)), q = photo_clamp01(mx * (1.0f - s * f)), t = photo_clamp01(mx * (1.0f - s * (1.0f - f)));
+  r = sec == 0 || sec == 5 ? mx : (sec == 1 ? q : (sec == 4 ? t : p));
+  g = sec == 1 || sec == 2 ? mx : (sec == 0 ? t : (sec == 3 ? q : p));
+  b = sec == 3 || sec == 4 ? mx : (sec == 2 ? t : (sec == 5 ? q : p));
+}
+
+// Statistics pass of the contrast step: for every sample with contrast != 1, ws[b * gridDim.x + blockIdx.x] = the sum of g(x) after
+// step 1 over this workgroup's PHOTO_BLOCK pixel quads, always in the same order: a thread adds its four pixels left to right, a
+// wavefront halves six times (lane l += lane l + 32, 16, ... 1), thread 0 adds the four wavefronts' sums in order.  The resample is
+// taken unmirrored: the mean over all pixels does not depend on the mirror, and so neither do its bits.
+__global__ __launch_bounds__(PHOTO_BLOCK) void clip_photo_stats_kernel(const uint8_t* __restrict__ cache, int64_t row_bytes,
+                                                                       const int64_t* __restrict__ idx,
+                                                                       const d2r_clip_augment_desc* __restrict__ aug,
+                                                                       const d2r_clip_photo_desc* __restrict__ photo, int S, int quads,
+                                                                       float rescale, float* __restrict__ ws) {
+  __shared__ float sw[PHOTO_BLOCK / 64];
+  const d2r_clip_photo_desc ph = photo[blockIdx.y];  // uniform: scalar loads
+  if (ph.contrast == 1.0f) return;                   // the whole workgroup: the apply kernel does not read this sample's partials
+  const d2r_clip_augment_desc d = aug[blockIdx.y];
+  const int t = blockIdx.x * PHOTO_BLOCK + threadIdx.x;  // < 4096 * 1024
+  float s = 0.0f;
+  if (t < S * quads) {
+    const int i = t / quads, j0 = (t - i * quads) * 4;
+    float x[3][4];
+    photo_resample(cache + idx[blockIdx.y] * row_bytes, d, 0, i, j0, S, rescale, x);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (ph.brightness != 1.0f) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x[c][k] = photo_brightness(x[c][k], ph.brightness);
+      }
+      if (j0 + k < S) s += photo_gray(x[0][k], x[1][k], x[2][k]);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) s += __shfl_down(s, off, 64);
+  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) ws[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = ((sw[0] + sw[1]) + sw[2]) + sw[3];
+}
+
+// out[b, :, i, j0 .. j0 + 3] for one thread: the resample, steps 1 to 7 of K22 on the three channels together, three float4 under
+// K21's alignment rule (single stores otherwise).  `parts` partial sums per sample are added in index order for the contrast mean.
+struct photo_norm {
+  float mean[3], std[3];
+};
+__global__ __launch_bounds__(PHOTO_BLOCK) void clip_photo_apply_kernel(const uint8_t* __restrict__ cache, int64_t row_bytes,
+                                                                       const int64_t* __restrict__ idx,
+                                                                       const d2r_clip_augment_desc* __restrict__ aug,
+                                                                       const d2r_clip_photo_desc* __restrict__ photo, int S, int quads,
+                                                                       float rescale, photo_norm nm, const float* __restrict__ ws,
+                                                                       int parts, float* __restrict__ out) {
+  const d2r_clip_augment_desc d = aug[blockIdx.y];   // uniform: scalar loads
+  const d2r_clip_photo_desc ph = photo[blockIdx.y];
+  const int t = blockIdx.x * PHOTO_BLOCK + threadIdx.x;
+  if (t >= S * quads) return;
+  const int i = t / quads, j0 = (t - i * quads) * 4;
+  const int plane = S * S;
+  float x[3][4];
+  photo_resample(cache + idx[blockIdx.y] * row_bytes, d, d.flip, i, j0, S, rescale, x);
+  float m = 0.0f;
+  if (ph.contrast != 1.0f) {
+    const float* w = ws + (int64_t)blockIdx.y * parts;
+    m = w[0];
+    for (int q = 1; q < parts; ++q) m += w[q];
+    m = m / (float)plane;  // S * S <= 2^24 is exact
+  }
+  const bool erase_row = ph.ew > 0 && i >= ph.ey0 && i < ph.ey0 + ph.eh;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float r = x[0][k], g = x[1][k], b = x[2][k];
+    if (ph.brightness != 1.0f) {
+      r = photo_brightness(r, ph.brightness);
+      g = photo_brightness(g, ph.brightness);
+      b = photo_brightness(b, ph.brightness);
+    }
+    if (ph.contrast != 1.0f) {
+      const float km = (1.0f - ph.contrast) * m;
+      r = photo_clamp01(ph.contrast * r + km);
+      g = photo_clamp01(ph.contrast * g + km);
+      b = photo_clamp01(ph.contrast * b + km);
+    }
+    if (ph.saturation != 1.0f) {
+      const float sg = (1.0f - ph.saturation) * photo_gray(r, g, b);
+      r = photo_clamp01(ph.saturation * r + sg);
+      g = photo_clamp01(ph.saturation * g + sg);
+      b = photo_clamp01(ph.saturation * b + sg);
+    }
+    if (ph.hue != 0.0f) photo_hue(r, g, b, ph.hue);
+    if (ph.gray) r = g = b = photo_gray(r, g, b);
+    const bool erased = erase_row && j0 + k >= ph.ex0 && j0 + k < ph.ex0 + ph.ew;
+    x[0][k] = erased ? 0.0f : (r - nm.mean[0]) / nm.std[0];
+    x[1][k] = erased ? 0.0f : (g - nm.mean[1]) / nm.std[1];
+    x[2][k] = erased ? 0.0f : (b - nm.mean[2]) / nm.std[2];
+  }
+  float* o = out + (int64_t)blockIdx.y * 3 * plane + (int64_t)i * S + j0;
+  if ((S & 3) == 0 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) {  // plane is a multiple of 4 then: all three channels aligned
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<float4*>(o + (int64_t)c * plane) = make_float4(x[c][0], x[c][1], x[c][2], x[c][3]);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (j0 + k < S) o[(int64_t)c * plane + k] = x[c][k];
+  }
+}
+
 // dst[b] = src[idx[b]], rows of `elems` V-sized pieces
 template <typename V>
 __global__ __launch_bounds__(256) void gather_rows_kernel(V* __restrict__ dst, const V* __restrict__ src, int64_t elems,
@@ -222,6 +381,17 @@ int launch_gather_rows(void* dst, const void* src, int64_t row_bytes, const int6
 int check_rows(const char* who, const char* what, const int64_t* h, int B, int64_t rows) {
   for (int b = 0; b < B; ++b)
     D2R_REQUIRE(h[b] >= 0 && h[b] < rows, "%s: %s %d is %lld, outside the %lld rows", who, what, b, (long long)h[b], (long long)rows);
+  return D2R_OK;
+}
+
+// every box inside the S x S crop, every flip 0 or 1
+int check_boxes(const char* who, const d2r_clip_augment_desc* h, int B, int S) {
+  for (int b = 0; b < B; ++b) {
+    const d2r_clip_augment_desc& d = h[b];
+    D2R_REQUIRE(d.x0 >= 0 && d.y0 >= 0 && d.w >= 1 && d.h >= 1 && d.w <= S && d.h <= S && d.x0 <= S - d.w && d.y0 <= S - d.h,
+                "%s: sample %d: the %d x %d box at (%d, %d) does not lie inside the %d x %d crop", who, b, d.w, d.h, d.x0, d.y0, S, S);
+    D2R_REQUIRE(d.flip == 0 || d.flip == 1, "%s: sample %d: flip is %d, not 0 or 1", who, b, d.flip);
+  }
   return D2R_OK;
 }
 
@@ -347,17 +517,71 @@ extern "C" int d2r_clip_cache_augment(const uint8_t* cache, int64_t cache_rows, 
                   (reinterpret_cast<uintptr_t>(lut) & 3u) == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0,
               "d2r_clip_cache_augment: cache must be 16-byte, idx 8-byte, aug / lut / out 4-byte aligned");
   if (int rc = check_rows("d2r_clip_cache_augment", "index", h_idx, B, cache_rows)) return rc;
-  for (int b = 0; b < B; ++b) {
-    const d2r_clip_augment_desc& d = h_aug[b];
-    D2R_REQUIRE(d.x0 >= 0 && d.y0 >= 0 && d.w >= 1 && d.h >= 1 && d.w <= S && d.h <= S && d.x0 <= S - d.w && d.y0 <= S - d.h,
-                "d2r_clip_cache_augment: sample %d: the %d x %d box at (%d, %d) does not lie inside the %d x %d crop", b, d.w, d.h, d.x0,
-                d.y0, S, S);
-    D2R_REQUIRE(d.flip == 0 || d.flip == 1, "d2r_clip_cache_augment: sample %d: flip is %d, not 0 or 1", b, d.flip);
-  }
+  if (int rc = check_boxes("d2r_clip_cache_augment", h_aug, B, S)) return rc;
   const int quads = (S + 3) / 4;
   hipLaunchKernelGGL(clip_cache_augment_kernel, dim3(d2r_cdiv((int64_t)3 * S * quads, 256), B), dim3(256), 0, (hipStream_t)stream, cache,
                      (int64_t)d2r_clip_cache_row_bytes(S), idx, aug, S, quads, lut, out);
   return d2r_check_launch("d2r_clip_cache_augment");
+}
+
+// partial sums per sample of the statistics pass: one per workgroup of PHOTO_BLOCK pixel quads
+static int photo_parts(int S) { return d2r_cdiv((int64_t)S * ((S + 3) / 4), PHOTO_BLOCK); }
+
+extern "C" size_t d2r_clip_cache_augment_photo_ws_bytes(int B, int S) {
+  return B < 1 || S < 1 || S > 4096 ? 0 : (size_t)B * photo_parts(S) * sizeof(float);
+}
+
+extern "C" int d2r_clip_cache_augment_photo(const uint8_t* cache, int64_t cache_rows, const int64_t* h_idx, const int64_t* idx,
+                                            const d2r_clip_augment_desc* h_aug, const d2r_clip_augment_desc* aug,
+                                            const d2r_clip_photo_desc* h_photo, const d2r_clip_photo_desc* photo, int B, int S,
+                                            const float* h_norm, float rescale, float* out, void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "d2r_clip_cache_augment_photo";
+  D2R_REQUIRE(cache && h_idx && idx && h_aug && aug && h_photo && photo && h_norm && out && ws, "%s: null pointer", who);
+  D2R_REQUIRE(B >= 1 && B <= 65535 && S >= 1 && S <= 4096 && cache_rows >= 1, "%s: bad batch %d, crop size %d or %lld cache rows", who, B, S,
+              (long long)cache_rows);
+  D2R_REQUIRE(d2r_aligned16(cache) && (reinterpret_cast<uintptr_t>(idx) & 7u) == 0 && (reinterpret_cast<uintptr_t>(aug) & 3u) == 0 &&
+                  (reinterpret_cast<uintptr_t>(photo) & 3u) == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0 &&
+                  (reinterpret_cast<uintptr_t>(ws) & 3u) == 0,
+              "%s: cache must be 16-byte, idx 8-byte, aug / photo / out / ws 4-byte aligned", who);
+  photo_norm nm;
+  for (int c = 0; c < 3; ++c) {
+    nm.mean[c] = h_norm[c];
+    nm.std[c] = h_norm[3 + c];
+    D2R_REQUIRE(std::isfinite(nm.mean[c]) && std::isfinite(nm.std[c]) && nm.std[c] > 0.0f, "%s: channel %d: mean %g, std %g (finite, std > 0)",
+                who, c, (double)nm.mean[c], (double)nm.std[c]);
+  }
+  D2R_REQUIRE(std::isfinite(rescale) && rescale > 0.0f, "%s: rescale is %g, not finite and > 0", who, (double)rescale);
+  if (int rc = check_rows(who, "index", h_idx, B, cache_rows)) return rc;
+  if (int rc = check_boxes(who, h_aug, B, S)) return rc;
+  bool stats = false;
+  for (int b = 0; b < B; ++b) {
+    const d2r_clip_photo_desc& p = h_photo[b];
+    const float f[3] = {p.brightness, p.contrast, p.saturation};
+    for (int k = 0; k < 3; ++k)
+      D2R_REQUIRE(std::isfinite(f[k]) && f[k] >= 0.0f, "%s: sample %d: %s factor %g is not finite and >= 0", who, b,
+                  k == 0 ? "brightness" : (k == 1 ? "contrast" : "saturation"), (double)f[k]);
+    D2R_REQUIRE(std::fabs(p.hue) <= 0.5f, "%s: sample %d: hue shift %g is outside [-0.5, 0.5]", who, b, (double)p.hue);
+    D2R_REQUIRE(p.gray == 0 || p.gray == 1, "%s: sample %d: gray is %d, not 0 or 1", who, b, p.gray);
+    D2R_REQUIRE(p.ew == 0 || (p.ex0 >= 0 && p.ey0 >= 0 && p.ew >= 1 && p.eh >= 1 && p.ew <= S && p.eh <= S && p.ex0 <= S - p.ew &&
+                              p.ey0 <= S - p.eh),
+                "%s: sample %d: the %d x %d erase box at (%d, %d) is neither empty (ew = 0) nor inside the %d x %d output", who, b, p.ew,
+                p.eh, p.ex0, p.ey0, S, S);
+    D2R_REQUIRE(p.reserved[0] == 0 && p.reserved[1] == 0 && p.reserved[2] == 0, "%s: sample %d: reserved fields must be zero", who, b);
+    stats = stats || p.contrast != 1.0f;
+  }
+  const size_t need = d2r_clip_cache_augment_photo_ws_bytes(B, S);
+  if (ws_bytes < need) return d2r_fail(D2R_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
+  const int quads = (S + 3) / 4, parts = photo_parts(S);
+  const int64_t row_bytes = (int64_t)d2r_clip_cache_row_bytes(S);
+  hipStream_t st = (hipStream_t)stream;
+  if (stats) {  // only when some sample's contrast factor is not 1
+    hipLaunchKernelGGL(clip_photo_stats_kernel, dim3(parts, B), dim3(PHOTO_BLOCK), 0, st, cache, row_bytes, idx, aug, photo, S, quads,
+                       rescale, (float*)ws);
+    if (int rc = d2r_check_launch("d2r_clip_cache_augment_photo (statistics pass)")) return rc;
+  }
+  hipLaunchKernelGGL(clip_photo_apply_kernel, dim3(parts, B), dim3(PHOTO_BLOCK), 0, st, cache, row_bytes, idx, aug, photo, S, quads,
+                     rescale, nm, (const float*)ws, parts, out);
+  return d2r_check_launch("d2r_clip_cache_augment_photo");
 }
 
 extern "C" int d2r_gather_rows(void* dst, const void* src, int64_t src_rows, int64_t row_bytes, const int64_t* h_idx, const int64_t* idx,

@@ -18,7 +18,8 @@ launches the kernels on the current stream.  ``reference_preprocess`` is the sam
 ``to_cache`` stops one step earlier: the uint8 crop goes into rows of a device-resident cache (``d2r_clip_preprocess_u8``), from
 which ``clip_cache_gather`` later builds the same pixel values by index (d2r_amd.cache, --cache_dataset device).
 ``clip_cache_augment`` is that gather with a box per sample resized bilinearly to S x S and an optional mirror (d2r_amd.augment);
-``reference_augment`` restates it in numpy float64.
+``reference_augment`` restates it in numpy float64.  ``clip_cache_augment_photo`` adds the photometric half (brightness, contrast,
+saturation, hue, grayscale, erase box: DESIGN.md K22) to the same resample of the raw values; ``reference_photo`` restates that.
 """
 from __future__ import annotations
 
@@ -319,6 +320,119 @@ def reference_augment(crop: np.ndarray, box, S: int, table: np.ndarray = None) -
         c_, d = T[np.ix_(y0 + iy1, x0 + ix0)], T[np.ix_(y0 + iy1, x0 + ix1)]
         out[c] = (1 - fy) * ((1 - fx) * a + fx * b) + fy * ((1 - fx) * c_ + fx * d)
     return out
+
+
+PHOTO_FIELDS = 12  # 32-bit words per d2r_clip_photo_desc: fp32 brightness, contrast, saturation, hue; int32 gray, ex0, ey0, ew, eh, 3 x 0
+assert 4 * PHOTO_FIELDS == C.sizeof(_lib.ClipPhotoDesc)
+GRAY_WEIGHTS = (0.299, 0.587, 0.114)  # g(x) of K22 (ITU-R 601 luma: torchvision's rgb_to_grayscale, Pillow's "L")
+
+
+def photo_desc(rows) -> torch.Tensor:
+    """Host int32 [B, 12] descriptors (the four factors as their fp32 bits) from rows (brightness, contrast, saturation, hue, gray,
+    ex0, ey0, ew, eh)."""
+    rows = np.asarray(rows, np.float64).reshape(-1, 9)
+    d = np.zeros((len(rows), PHOTO_FIELDS), np.int32)
+    d[:, :4] = rows[:, :4].astype(np.float32).view(np.int32)
+    d[:, 4:9] = rows[:, 4:].astype(np.int32)
+    return torch.from_numpy(d)
+
+
+def clip_cache_augment_photo_ws_bytes(B: int, S: int) -> int:
+    return int(_lib.load().d2r_clip_cache_augment_photo_ws_bytes(B, S))
+
+
+def clip_cache_augment_photo(cache: torch.Tensor, h_idx: torch.Tensor, idx: torch.Tensor, h_aug: torch.Tensor, aug: torch.Tensor,
+                             h_photo: torch.Tensor, photo: torch.Tensor, S: int, norm=(CLIP_MEAN, CLIP_STD, RESCALE),
+                             out: torch.Tensor = None, ws: torch.Tensor = None) -> torch.Tensor:
+    """d2r_clip_cache_augment_photo on the current stream: clip_cache_augment on the raw values (no table) followed per sample by
+    brightness, contrast, saturation, hue, grayscale, the normalisation with norm = (mean, std, rescale) and an erase box (K22).
+    photo is int32 [B, 12] on the device (``photo_desc``), h_photo its host copy; ws a float32 workspace of at least
+    clip_cache_augment_photo_ws_bytes(B, S) bytes on the device (allocated when None).  The library checks indices, boxes and
+    descriptors on the host copies before it enqueues anything."""
+    B = h_idx.numel()
+    dev = cache.device
+    if not (cache.dtype == torch.uint8 and h_idx.dtype == torch.int64 and idx.dtype == torch.int64 and h_aug.dtype == torch.int32 and
+            aug.dtype == torch.int32 and h_photo.dtype == torch.int32 and photo.dtype == torch.int32):
+        raise TypeError("cache uint8, idx int64, aug / photo int32 expected")
+    if cache.dim() != 2 or cache.shape[1] != cache_row_bytes(S) or idx.numel() != B or tuple(h_aug.shape) != (B, AUG_FIELDS) or \
+            tuple(aug.shape) != (B, AUG_FIELDS) or tuple(h_photo.shape) != (B, PHOTO_FIELDS) or tuple(photo.shape) != (B, PHOTO_FIELDS):
+        raise ValueError("cache / index / descriptor sizes disagree")
+    if not all(t.is_cuda and t.device == dev and t.is_contiguous() for t in (cache, idx, aug, photo)) or \
+            any(t.is_cuda or not t.is_contiguous() for t in (h_idx, h_aug, h_photo)):
+        raise ValueError("device tensors must be contiguous on one GPU, h_idx / h_aug / h_photo on the host")
+    mean, std, rescale = norm
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("norm must be (mean[3], std[3], rescale)")
+    need = clip_cache_augment_photo_ws_bytes(B, S)
+    if ws is None:
+        ws = torch.empty(max(need // 4, 1), dtype=torch.float32, device=dev)
+    elif ws.dtype != torch.float32 or not ws.is_contiguous() or ws.device != dev:
+        raise ValueError("ws must be a contiguous fp32 tensor on the cache's device")
+    if out is None:
+        out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * 3 * S * S or out.device != dev:
+        raise ValueError("out must be a contiguous fp32 [B, 3, S, S] tensor on the cache's device")
+    h_norm = (C.c_float * 6)(*[float(v) for v in mean], *[float(v) for v in std])
+    from .functional import _stream
+    _lib.call("d2r_clip_cache_augment_photo", cache.data_ptr(), cache.shape[0], h_idx.data_ptr(), idx.data_ptr(),
+              C.cast(h_aug.data_ptr(), C.POINTER(_lib.ClipAugmentDesc)), aug.data_ptr(),
+              C.cast(h_photo.data_ptr(), C.POINTER(_lib.ClipPhotoDesc)), photo.data_ptr(), B, S, h_norm, float(rescale), out.data_ptr(),
+              ws.data_ptr(), ws.numel() * 4, _stream())
+    return out
+
+
+def _gray64(x):
+    return GRAY_WEIGHTS[0] * x[0] + GRAY_WEIGHTS[1] * x[1] + GRAY_WEIGHTS[2] * x[2]
+
+
+def reference_hue(x: np.ndarray, delta: float) -> np.ndarray:
+    """Step 4 of K22 in float64 on x [3, ...] in [0, 1]: RGB -> HSV (hexcone), h <- frac(h + delta), HSV -> RGB."""
+    r, g, b = x[0], x[1], x[2]
+    mx, mn = np.maximum(np.maximum(r, g), b), np.minimum(np.minimum(r, g), b)
+    cr = mx - mn
+    grey = cr == 0
+    s = cr / np.where(grey, 1.0, mx)
+    dv = np.where(grey, 1.0, cr)
+    rc, gc, bc = (mx - r) / dv, (mx - g) / dv, (mx - b) / dv
+    h6 = np.where(mx == r, bc - gc, np.where(mx == g, 2.0 + rc - bc, 4.0 + gc - rc))
+    h = h6 / 6.0 + delta
+    h = h - np.floor(h)
+    hs = h * 6.0
+    fl = np.floor(hs)
+    f = hs - fl
+    sec = fl.astype(np.int64) % 6
+    p, q, t = mx * (1.0 - s), mx * (1.0 - s * f), mx * (1.0 - s * (1.0 - f))
+    p, q, t = (np.clip(v, 0.0, 1.0) for v in (p, q, t))
+    pick = lambda table: np.choose(sec, table)  # noqa: E731
+    return np.stack([pick([mx, q, p, p, t, mx]), pick([t, mx, mx, q, p, p]), pick([p, p, t, mx, mx, q])])
+
+
+def reference_photo(crop: np.ndarray, box, photo, S: int, mean=CLIP_MEAN, std=CLIP_STD) -> np.ndarray:
+    """CPU restatement of d2r_clip_cache_augment_photo for one sample, in float64 (K22): `crop` uint8 planar [3, S, S], `box` =
+    (x0, y0, w, h, flip), `photo` = (brightness, contrast, saturation, hue, gray, ex0, ey0, ew, eh) -> float64 [3, S, S].  The
+    resample is reference_augment's, of the raw values crop / 255."""
+    beta, kappa, sigma, delta = (float(v) for v in photo[:4])
+    gray, ex0, ey0, ew, eh = (int(v) for v in photo[4:9])
+    if not all(math.isfinite(v) and v >= 0 for v in (beta, kappa, sigma)) or not abs(delta) <= 0.5 or gray not in (0, 1):
+        raise ValueError(f"bad photometric settings {tuple(photo)}")
+    if ew != 0 and not (ex0 >= 0 and ey0 >= 0 and ew >= 1 and eh >= 1 and ex0 + ew <= S and ey0 + eh <= S):
+        raise ValueError(f"erase box {(ex0, ey0, ew, eh)} is neither empty nor inside the {S} x {S} output")
+    raw = np.tile(np.arange(256, dtype=np.float64) / 255.0, (3, 1))
+    x = reference_augment(crop, box, S, raw)
+    if beta != 1.0:
+        x = np.clip(beta * x, 0.0, 1.0)
+    if kappa != 1.0:
+        x = np.clip(kappa * x + (1.0 - kappa) * _gray64(x).mean(), 0.0, 1.0)
+    if sigma != 1.0:
+        x = np.clip(sigma * x + (1.0 - sigma) * _gray64(x)[None], 0.0, 1.0)
+    if delta != 0.0:
+        x = reference_hue(x, delta)
+    if gray:
+        x = np.repeat(_gray64(x)[None], 3, axis=0)
+    x = (x - np.asarray(mean, np.float64)[:, None, None]) / np.asarray(std, np.float64)[:, None, None]
+    if ew != 0:
+        x[:, ey0:ey0 + eh, ex0:ex0 + ew] = 0.0
+    return x
 
 
 def gather_rows(src: torch.Tensor, h_idx: torch.Tensor, idx: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:

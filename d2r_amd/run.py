@@ -15,6 +15,8 @@ allowed), --write_path writes the per-sample predictions as JSON Lines (MSDTrain
 --ema_decay D averages the weights inside the AdamW launch; the dev / test passes and best_model.pth use the average.
 --label_smoothing E / --class_weights {none | balanced | W0,W1,...} are the options of the cross entropy (inside its kernels).
 --aug_crop_scale LO / --aug_flip P (with --data_path) augment the training images on the device (d2r_amd.augment).
+--aug_brightness B / --aug_contrast C / --aug_saturation S / --aug_hue H / --aug_grayscale P / --aug_erase P: the photometric half of
+that augmentation (colour jitter in this fixed order, random grayscale, random erasing), in the same launch slot.
 --layer_lr_decay D / --wd_exempt_1d / --weight_decay W: AdamW hyper-parameters per parameter, still one launch (d2r_adamw_step_table).
 --drop_path P: stochastic depth of the two encoder towers, growing linearly with depth from 0 to P (d2r_drop_path), training only.
 """
@@ -89,6 +91,24 @@ def _aug_flip(text):
     if not 0 <= v <= 1:
         raise argparse.ArgumentTypeError(f"must be in [0, 1] (0 = no flipping), got {text}")
     return v
+
+
+def _aug_jitter(text):
+    v = float(text)
+    if not (v >= 0 and math.isfinite(v)):
+        raise argparse.ArgumentTypeError(f"must be finite and >= 0 (0 = off), got {text}")
+    return v
+
+
+def _aug_hue(text):
+    v = float(text)
+    if not 0 <= v <= 0.5:
+        raise argparse.ArgumentTypeError(f"must be in [0, 0.5] (0 = off), got {text}")
+    return v
+
+
+PHOTO_FLAGS = ("aug_brightness", "aug_contrast", "aug_saturation", "aug_hue", "aug_grayscale", "aug_erase")
+_PHOTO_NAMES = " / ".join("--" + f for f in PHOTO_FLAGS)
 
 
 def _drop_path(text):
@@ -241,6 +261,17 @@ def build_parser():
                    "crop size (torchvision's RandomResizedCrop); in (0, 1], 1 = off, the reference's behaviour")
     p.add_argument("--aug_flip", default=0.0, type=_aug_flip, help="with --data_path: mirror each training image horizontally with "
                    "this probability, in [0, 1] (0 = off, the reference's behaviour); dev and test images are never augmented")
+    for name, what in (("brightness", "brightness"), ("contrast", "contrast"), ("saturation", "saturation")):
+        p.add_argument(f"--aug_{name}", default=0.0, type=_aug_jitter, help=f"with --data_path: scale the {what} of each training image "
+                       "by a factor drawn uniformly from [max(0, 1 - J), 1 + J] (torchvision's ColorJitter; applied in the fixed order "
+                       "brightness, contrast, saturation, hue); finite and >= 0, 0 = off; same rules as --aug_flip")
+    p.add_argument("--aug_hue", default=0.0, type=_aug_hue, help="with --data_path: shift the hue of each training image by a fraction "
+                   "of a turn drawn uniformly from [-H, H]; in [0, 0.5], 0 = off")
+    p.add_argument("--aug_grayscale", default=0.0, type=_aug_flip, help="with --data_path: turn each training image grey with this "
+                   "probability (torchvision's RandomGrayscale); in [0, 1], 0 = off")
+    p.add_argument("--aug_erase", default=0.0, type=_aug_flip, help="with --data_path: with this probability, zero a random box of "
+                   "2 %% to 33 %% of each normalised training image, aspect ratio 0.3 to 3.3 (torchvision's RandomErasing); in [0, 1], "
+                   "0 = off")
     p.add_argument("--pretrained", action="store_true", help="model configs, weights and image preprocessing from the local "
                    "--bert_name / --vit_name checkpoints (BertModel, CLIPModel.vision_model, preprocessor_config.json)")
     return p
@@ -283,6 +314,11 @@ def main(argv=None):
     if augment and args.data_path is None:
         raise SystemExit("--aug_crop_scale / --aug_flip augment the uint8 crops of the images of --data_path: synthetic images are "
                          "not such crops; run without them")
+    photo = {f[4:]: getattr(args, f) for f in PHOTO_FLAGS}
+    photometric = any(v > 0.0 for v in photo.values())
+    if photometric and args.data_path is None:
+        raise SystemExit(f"{_PHOTO_NAMES} augment the uint8 crops of the images of --data_path: synthetic images are not such crops; "
+                         "run without them")
     try:
         class_weights = parse_class_weights(args.class_weights, args.num_classes)
     except ValueError as e:
@@ -349,11 +385,21 @@ def main(argv=None):
     augmenter = None
     if augment and args.only_test:
         logger.info("--aug_crop_scale / --aug_flip are ignored with --only_test: only training batches are augmented")
-    elif augment:
-        # a generator of its own, seeded from (--seed, rank): each rank augments its shard with its own stream, and the default
-        # generator (samplers, dropout seeds) is never drawn from
+    if photometric and args.only_test:
+        logger.info("%s are ignored with --only_test: only training batches are augmented", _PHOTO_NAMES)
+    elif photometric and float(rescale) != RESCALE:
+        raise SystemExit(f"{_PHOTO_NAMES} work on pixel values in [0, 1] and need the preprocessor's rescale_factor to be 1/255, "
+                         f"got rescale_factor = {rescale!r}")
+    if (augment or photometric) and not args.only_test:
+        # generators of its own, seeded from (--seed, rank): each rank augments its shard with its own streams, and the default
+        # generator (samplers, dropout seeds) is never drawn from; the photometric options alone leave the boxes the identity
         from .augment import Augmenter
-        augmenter = Augmenter(S, args.aug_crop_scale, args.aug_flip, seed=args.seed, rank=rank)
+        if photometric:
+            augmenter = Augmenter(S, args.aug_crop_scale, args.aug_flip, seed=args.seed, rank=rank, brightness=photo["brightness"],
+                                  contrast=photo["contrast"], saturation=photo["saturation"], hue=photo["hue"],
+                                  grayscale_p=photo["grayscale"], erase_p=photo["erase"], norm=(mean, std, rescale))
+        else:
+            augmenter = Augmenter(S, args.aug_crop_scale, args.aug_flip, seed=args.seed, rank=rank)
     if args.cache_dataset == "device" and args.only_test:
         logger.info("--cache_dataset device is ignored with --only_test: a single pass over the test split gains nothing")
     elif args.cache_dataset == "device":

@@ -13,8 +13,9 @@ state-dict key names (:210-216).  Differences, all deliberate (SURVEY.md Appendi
     the averaged weights and best_model.pth holds them; BatchNorm running statistics stay the live ones), layer-wise lr decay and
     no weight decay on 1-D parameters (args.layer_lr_decay, args.wd_exempt_1d), the weight decay itself (args.weight_decay),
     stochastic depth of the two encoder towers in training steps (args.drop_path; its seeds come from a generator of its own);
-  * optional image augmentation of the TRAINING batches (``augmenter``, d2r_amd.augment: random resized crop and flip on the
-    device; a CachedLoader carries its own); evaluate() / test() / predict() never augment;
+  * optional image augmentation of the TRAINING batches (``augmenter``, d2r_amd.augment: random resized crop and flip, colour
+    jitter, random grayscale and random erasing on the device; a CachedLoader carries its own); evaluate() / test() / predict()
+    never augment;
   * evaluate() / test() count a confusion matrix on the device (d2r_confusion_add) instead of copying labels and predictions to
     the host per batch, and log per-class precision / recall / F1 / support after the four aggregates; they return the scalar
     entries as before, the whole result (with "confusion" and "per_class") stays in last_dev_result / last_test_result.

@@ -682,6 +682,45 @@ typedef struct {
 int d2r_clip_cache_augment(const uint8_t* cache, int64_t cache_rows, const int64_t* h_idx, const int64_t* idx,
                            const d2r_clip_augment_desc* h_aug, const d2r_clip_augment_desc* aug, int B, int S, const float* lut,
                            float* out, void* stream);
+/* K22  Photometric augmentation on the cache rows (d2r_amd/augment.py, --aug_brightness / --aug_contrast / --aug_saturation /
+ * --aug_hue / --aug_grayscale / --aug_erase).  d2r_clip_cache_augment_photo is d2r_clip_cache_augment on the RAW values: for sample b,
+ * x[c,i,j] is K21's resample (the same box, taps, fx / fy, blend and mirror) of float(P[c,.,.]) * rescale in place of the table's
+ * entries, a value in [0, 1]; then, in this fixed order, with g(x) = 0.299*x_R + 0.587*x_G + 0.114*x_B and clamp to [0, 1]:
+ *   1. brightness: x <- clamp(brightness * x);
+ *   2. contrast:   m = mean of g(x) over the S*S pixels of the sample after step 1;  x <- clamp(contrast * x + (1 - contrast) * m);
+ *   3. saturation: x <- clamp(saturation * x + (1 - saturation) * g(x)) per pixel;
+ *   4. hue:        RGB -> HSV by the hexcone formulas (v = max, s = (max - min) / max, s = 0 when max = 0; h = 0 when max = min,
+ *                  else ((G-B)/(max-min) | 2 + (B-R)/(max-min) | 4 + (R-G)/(max-min)) / 6 by which channel is the maximum, R first),
+ *                  h <- frac(h + hue), HSV -> RGB;
+ *   5. gray = 1:   all three channels <- g(x);
+ *   6. normalise:  (x - mean[c]) / std[c];
+ *   7. erase box:  output pixels ex0 <= j < ex0 + ew, ey0 <= i < ey0 + eh become 0.0f in all channels (ew = 0: none).
+ * Steps 1 - 3 are torchvision's float-tensor adjust_brightness / adjust_contrast / adjust_saturation, step 4 its adjust_hue, step 7
+ * its RandomErasing(value=0) after Normalize; the order is fixed (the random permutation torchvision's ColorJitter draws is not
+ * built).  A step whose factor is the identity (brightness, contrast, saturation = 1, hue = 0) is skipped, so a sample with everything
+ * off is fl(fl(x - mean[c]) / std[c]) of the resample, and with the identity box x = fl(float(P) * rescale).  fp32 throughout.
+ *   h_norm : HOST array of six floats, mean[0..3) then std[0..3) (std > 0); they and rescale reach the kernel by value;
+ *   ws     : float workspace, >= d2r_clip_cache_augment_photo_ws_bytes(B, S) bytes: ceil(S * ceil(S/4) / 256) partial sums of g per
+ *            sample.  It is written and read only when some sample of the batch has contrast != 1 (a pass of its own recomputes the
+ *            resample and step 1 and adds g in a fixed order: no floating-point atomics, a second run gives the same bits);
+ *   out    : fp32 [B, 3, S, S], OVERWRITTEN.
+ * One d2r_clip_photo_desc per output sample, 48 bytes, next to its d2r_clip_augment_desc.  h_idx / h_aug / h_photo are the host
+ * copies of idx / aug / photo: everything d2r_clip_cache_augment refuses, a factor that is negative or not finite, |hue| > 0.5, a gray
+ * other than 0 / 1, an erase box that is neither empty nor inside S x S, a non-zero reserved field, a mean / std / rescale that is not
+ * finite (std, rescale > 0) or a short workspace (D2R_ERR_WORKSPACE) is refused before anything is enqueued; a refused call writes
+ * nothing. */
+typedef struct {
+  float brightness, contrast, saturation; /* factors >= 0; 1 = off */
+  float hue;                              /* shift in turns, |hue| <= 0.5; 0 = off */
+  int32_t gray;                           /* 1: grayscale */
+  int32_t ex0, ey0, ew, eh;               /* erase box in output coordinates (column, row, width, height); ew = 0: none */
+  int32_t reserved[3];                    /* zero */
+} d2r_clip_photo_desc;
+size_t d2r_clip_cache_augment_photo_ws_bytes(int B, int S);
+int d2r_clip_cache_augment_photo(const uint8_t* cache, int64_t cache_rows, const int64_t* h_idx, const int64_t* idx,
+                                 const d2r_clip_augment_desc* h_aug, const d2r_clip_augment_desc* aug,
+                                 const d2r_clip_photo_desc* h_photo, const d2r_clip_photo_desc* photo, int B, int S, const float* h_norm,
+                                 float rescale, float* out, void* ws, size_t ws_bytes, void* stream);
 /* K19  Baseline JPEG decoding of a batch of images on the device (processor/dataset.py:89: Image.open(p).convert("RGB") in the
  * reference's loader workers), bit-identical to libjpeg-turbo's default path as Pillow uses it: Huffman decoding, ISLOW IDCT with
  * its range-limit table, fancy h2v1 / h2v2 chroma upsampling, fixed-point YCbCr -> RGB.  The host (d2r_amd/jpeg.py) parses the
