@@ -445,16 +445,21 @@ typedef struct {
   const void* dy;             /* bwd in  [B*L,E] */
   void* dx;                   /* bwd out [B*L,E] */
   void* scratch; size_t scratch_bytes;           /* bwd: >= d2r_encoder_layer_bwd_scratch() */
-  void* splitk_ws; size_t splitk_bytes;          /* bwd: split-K scratch of the weight-gradient GEMMs (may be NULL) */
+  /* bwd: split-K scratch of the in-call weight-gradient GEMMs (d2r_gemm_desc.workspace and its rules: the last 4 KiB zero before the
+   * first use, zero again afterwards; launches that share it are ordered).  NULL: those GEMMs run without split-K - same dx, o_dy[] and
+   * LayerNorm gradients bit for bit, dW / db summed in another order.  Not used with defer_wgrad. */
+  void* splitk_ws; size_t splitk_bytes;
   /* bwd: optional second stream (hipStream_t) for the four weight-gradient GEMMs, forked from `stream` inside the
-   * call; the caller joins it before anything reads the gradient sinks, and keeps x, the saved activations, dy and
-   * scratch alive until it has drained.  NULL: everything on `stream`. */
+   * call; the caller joins it before anything reads the gradient sinks, and keeps x, the saved activations, dy,
+   * scratch, splitk_ws (then used on that stream only) and the sinks alive until it has drained.  NULL: everything on `stream`. */
   void* wgrad_stream;
   /* bwd: != 0 skips the four weight-gradient GEMMs (and bias gradients); the caller launches them later, grouped with
    * the same products of other layers (d2r_gemm_tn_grouped), from o_dy[] and the saved activations. */
   int defer_wgrad;
   /* bwd, written by the call: the output gradients of the qkv / out / fc1 / fc2 linears ([T,3E] [T,E] [T,F] [T,E], inside
-   * `scratch` or dy itself) — dW = o_dy^T x with x = x|n1, ctx, n1|h2, f. */
+   * `scratch` or dy itself) — dW = o_dy^T x with x = x|n1, ctx, n1|h2, f.  With p_hidden or p_path, o_dy[1] and o_dy[3] name the
+   * MASKED gradients (mask o g / ((1 - p_hidden)(1 - p_path)): what the dense outputs receive), which are copies inside `scratch`;
+   * without them o_dy[3] of a pre-LN layer is dy itself.  They stay valid until `scratch` is reused. */
   const void* o_dy[4];
   /* bwd, with defer_wgrad: != 0 also defers the second stage of the two LayerNorm backward passes (their gamma / beta gradients):
    * the call writes the per-block partial sums into `scratch` and reports them in o_lnws[0] (LayerNorm 1) / o_lnws[1] (LayerNorm 2);
