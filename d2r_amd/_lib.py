@@ -213,6 +213,7 @@ SIGNATURES = {
     "d2r_clip_cache_augment_photo_ws_bytes": (sz, [i32, i32]),
     "d2r_clip_cache_augment_photo": (i32, [vp, i64, vp, vp, C.POINTER(ClipAugmentDesc), vp, C.POINTER(ClipPhotoDesc), vp, i32, i32,
                                            C.POINTER(f32), f32, vp, vp, sz, vp]),
+    "d2r_token_augment": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, i32, vp, i64, i64, i64, vp, vp, vp, vp]),
     "d2r_jpeg_decode_ws_bytes": (sz, [C.POINTER(JpegImageDesc), i32]),
     "d2r_jpeg_decode": (i32, [vp, i64, C.POINTER(JpegImageDesc), vp, i32, C.POINTER(JpegSegment), vp, i32, vp, vp, i64,
                               vp, i64, vp, vp, vp, sz, vp]),

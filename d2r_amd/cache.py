@@ -20,7 +20,9 @@ without.
 The cache holds the un-augmented crops.  A training loader may carry an ``Augmenter`` (d2r_amd.augment, --aug_crop_scale /
 --aug_flip): its batches' pixel values then come from d2r_clip_cache_augment, the same launch with a box and a flip per sample -
 or, with a photometric option on (--aug_brightness / --aug_contrast / --aug_saturation / --aug_hue / --aug_grayscale / --aug_erase),
-from d2r_clip_cache_augment_photo, which also jitters the colours, greys and erases per sample.
+from d2r_clip_cache_augment_photo, which also jitters the colours, greys and erases per sample.  It may also carry a
+``TokenAugmenter`` (d2r_amd.text_augment, --aug_token_delete / --aug_token_mask / --aug_token_replace): one d2r_token_augment launch
+then takes the place of the three d2r_gather_rows of the token tensors and deletes, masks or replaces tokens on the way (K23).
 """
 from __future__ import annotations
 
@@ -155,18 +157,22 @@ class DeviceDatasetCache:
         torch.cuda.synchronize(self.device)
         self.decode_log.end_pass(f"{self.split} split prefill")
 
-    def gather(self, h_idx: torch.Tensor, idx: torch.Tensor, augmenter=None):
+    def gather(self, h_idx: torch.Tensor, idx: torch.Tensor, augmenter=None, text_augmenter=None):
         """The trainer's 6-tuple of the samples idx (int64 [B] on the device, h_idx its host copy), on the device.  With an
-        `augmenter` (d2r_amd.augment.Augmenter) the pixel values are its augmented view of the crops."""
+        `augmenter` (d2r_amd.augment.Augmenter) the pixel values are its augmented view of the crops; with a `text_augmenter`
+        (d2r_amd.text_augment.TokenAugmenter) the three token tensors are its augmented view of the rows, from one launch."""
         if augmenter is None:
             images = I.clip_cache_gather(self.crops, h_idx, idx, self.S, self.lut)
         else:
             if augmenter.photometric and augmenter.norm != self.norm:  # the photometric kernel normalises by value, not by the table
                 raise ValueError(f"the {self.split} cache is normalised with {self.norm}, the augmenter was built with {augmenter.norm}")
             images = augmenter.apply(self.crops, h_idx, idx, self.lut)
-        batch = CachedBatch((I.gather_rows(self.input_ids, h_idx, idx), I.gather_rows(self.input_mask, h_idx, idx),
-                             I.gather_rows(self.segment_ids, h_idx, idx), self.img_mask.expand(h_idx.numel(), -1),
-                             I.gather_rows(self.labels, h_idx, idx), images))
+        if text_augmenter is None:
+            tokens = (I.gather_rows(self.input_ids, h_idx, idx), I.gather_rows(self.input_mask, h_idx, idx),
+                      I.gather_rows(self.segment_ids, h_idx, idx))
+        else:
+            tokens = text_augmenter.apply(self.input_ids, self.input_mask, self.segment_ids, h_idx, idx)
+        batch = CachedBatch((*tokens, self.img_mask.expand(h_idx.numel(), -1), I.gather_rows(self.labels, h_idx, idx), images))
         batch.cached_images = int(h_idx.numel())
         return batch
 
@@ -222,10 +228,11 @@ class CachedLoader:
     every epoch, or once when it keeps persistent workers - and the samplers draw theirs as they are iterated.  The same draws are
     made here, in the same order, so the state of the default generator after an epoch equals the plain loader's.
 
-    `augmenter` (training loader only): every batch's images are drawn through it, one draw per batch in batch order."""
+    `augmenter` (training loader only): every batch's images are drawn through it, one draw per batch in batch order.
+    `text_augmenter` (training loader only): likewise every batch's token tensors."""
 
-    def __init__(self, loader, cache, augmenter=None):
-        self.loader, self.cache, self.augmenter = loader, cache, augmenter
+    def __init__(self, loader, cache, augmenter=None, *, text_augmenter=None):
+        self.loader, self.cache, self.augmenter, self.text_augmenter = loader, cache, augmenter, text_augmenter
         self._persistent = bool(loader.persistent_workers and loader.num_workers > 0)
         self._started = False
 
@@ -255,13 +262,16 @@ class CachedLoader:
             if pin:
                 h_idx = h_idx.pin_memory()
             idx = h_idx.to(self.cache.device, non_blocking=True)
-            yield self.cache.gather(h_idx, idx) if self.augmenter is None else self.cache.gather(h_idx, idx, self.augmenter)
+            if self.text_augmenter is not None:
+                yield self.cache.gather(h_idx, idx, self.augmenter, text_augmenter=self.text_augmenter)
+            else:
+                yield self.cache.gather(h_idx, idx) if self.augmenter is None else self.cache.gather(h_idx, idx, self.augmenter)
 
 
-def cache_loaders(loaders: dict, device, logger=None, augmenters: dict = None) -> dict:
+def cache_loaders(loaders: dict, device, logger=None, augmenters: dict = None, *, text_augmenters: dict = None) -> dict:
     """{split: DataLoader} -> {split: CachedLoader}: every split's cache is sized and checked against the free device memory
     before anything is decoded, then allocated and prefilled in turn.  augmenters: {split: Augmenter} for the splits whose batches
-    are augmented (the training split, if any)."""
+    are augmented (the training split, if any); text_augmenters: {split: TokenAugmenter} likewise for the token tensors."""
     logger = logger or _logger
     needs = []
     for split, dl in loaders.items():
@@ -274,4 +284,5 @@ def cache_loaders(loaders: dict, device, logger=None, augmenters: dict = None) -
     caches = {split: DeviceDatasetCache.for_loader(dl, device, split, logger) for split, dl in loaders.items()}
     for split, dl in loaders.items():
         prefill(dl, caches[split], logger, split)
-    return {split: CachedLoader(dl, caches[split], (augmenters or {}).get(split)) for split, dl in loaders.items()}
+    return {split: CachedLoader(dl, caches[split], (augmenters or {}).get(split), text_augmenter=(text_augmenters or {}).get(split))
+            for split, dl in loaders.items()}

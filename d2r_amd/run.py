@@ -19,6 +19,9 @@ allowed), --write_path writes the per-sample predictions as JSON Lines (MSDTrain
 that augmentation (colour jitter in this fixed order, random grayscale, random erasing), in the same launch slot.
 --layer_lr_decay D / --wd_exempt_1d / --weight_decay W: AdamW hyper-parameters per parameter, still one launch (d2r_adamw_step_table).
 --drop_path P: stochastic depth of the two encoder towers, growing linearly with depth from 0 to P (d2r_drop_path), training only.
+--aug_token_delete P / --aug_token_mask P / --aug_token_replace P / --aug_whole_word: per token of a training text, delete it, put
+[MASK] in its place or replace it by a random id, per piece or per whole word, in the one launch that builds the batch's token
+tensors on the device (d2r_token_augment, d2r_amd.text_augment); real and synthetic data.
 """
 from __future__ import annotations
 
@@ -107,8 +110,40 @@ def _aug_hue(text):
     return v
 
 
+def _aug_token(text):
+    v = float(text)
+    if not 0 <= v <= 1:
+        raise argparse.ArgumentTypeError(f"must be in [0, 1] (0 = off), got {text}")
+    return v
+
+
 PHOTO_FLAGS = ("aug_brightness", "aug_contrast", "aug_saturation", "aug_hue", "aug_grayscale", "aug_erase")
 _PHOTO_NAMES = " / ".join("--" + f for f in PHOTO_FLAGS)
+
+
+TOKEN_FLAGS = ("aug_token_delete", "aug_token_mask", "aug_token_replace")
+_TOKEN_NAMES = " / ".join("--" + f for f in TOKEN_FLAGS)
+SYNTHETIC_TOKENS = dict(mask_id=103, pad_id=0, replace_range=(1000, 30000))  # SyntheticMSDDataset's ids: bert-base-uncased's layout
+
+
+def token_settings(tokenizer, whole_word: bool, need_mask: bool):
+    """TokenAugmenter's settings from a BertTokenizer: mask_id, pad_id, vocab = len(tokenizer), replace_range = (lo, vocab) with lo one
+    past the largest id among the special tokens and the tokens spelled [unusedN], cont = continuation_table with `whole_word`.
+    A tokenizer without a mask token is refused (SystemExit) when `need_mask`; its mask id is then the pad id (never written)."""
+    import re
+    from .text_augment import continuation_table
+    if tokenizer.mask_token_id is None and need_mask:
+        raise SystemExit("--aug_token_mask needs a tokenizer with a mask token: the one of --bert_name has none")
+    if tokenizer.pad_token_id is None:
+        raise SystemExit(f"{_TOKEN_NAMES} need a tokenizer with a padding token: the one of --bert_name has none")
+    reserved = list(tokenizer.all_special_ids) + [i for t, i in tokenizer.get_vocab().items() if re.fullmatch(r"\[unused\d+\]", t)]
+    vocab = len(tokenizer)
+    lo = 1 + max(reserved)
+    if lo >= vocab:
+        raise SystemExit(f"{_TOKEN_NAMES}: the vocabulary of --bert_name holds no id past its special and [unusedN] tokens to replace by")
+    mask_id = tokenizer.mask_token_id if tokenizer.mask_token_id is not None else tokenizer.pad_token_id
+    return dict(mask_id=int(mask_id), pad_id=int(tokenizer.pad_token_id), vocab=vocab, replace_range=(lo, vocab),
+                cont=continuation_table(tokenizer) if whole_word else None)
 
 
 def _drop_path(text):
@@ -272,6 +307,14 @@ def build_parser():
     p.add_argument("--aug_erase", default=0.0, type=_aug_flip, help="with --data_path: with this probability, zero a random box of "
                    "2 %% to 33 %% of each normalised training image, aspect ratio 0.3 to 3.3 (torchvision's RandomErasing); in [0, 1], "
                    "0 = off")
+    for name, what in (("delete", "delete it"), ("mask", "put [MASK] in its place"),
+                       ("replace", "replace it by an id drawn uniformly from the vocabulary past its special and [unusedN] tokens")):
+        p.add_argument(f"--aug_token_{name}", default=0.0, type=_aug_token, help="per token of a training text, with this "
+                       f"probability: {what}, on the device (d2r_token_augment); [CLS] and [SEP] are kept, and a text keeps its "
+                       "tokens if all would be deleted; in [0, 1], the three probabilities sum to at most 1, 0 = off, the reference's "
+                       "behaviour; dev and test texts are never augmented; real and synthetic data")
+    p.add_argument("--aug_whole_word", action="store_true", help="with --data_path: a word and its ## pieces share one --aug_token_* "
+                   "decision, drawn at the word's first piece")
     p.add_argument("--pretrained", action="store_true", help="model configs, weights and image preprocessing from the local "
                    "--bert_name / --vit_name checkpoints (BertModel, CLIPModel.vision_model, preprocessor_config.json)")
     return p
@@ -319,6 +362,13 @@ def main(argv=None):
     if photometric and args.data_path is None:
         raise SystemExit(f"{_PHOTO_NAMES} augment the uint8 crops of the images of --data_path: synthetic images are not such crops; "
                          "run without them")
+    token_p = [getattr(args, f) for f in TOKEN_FLAGS]
+    token_aug = any(v > 0.0 for v in token_p)
+    if sum(token_p) > 1.0:
+        raise SystemExit(f"{_TOKEN_NAMES} are the probabilities of one choice per token: their sum {sum(token_p):g} must be <= 1")
+    if args.aug_whole_word and args.data_path is None:
+        raise SystemExit("--aug_whole_word reads the word pieces from the vocabulary of --bert_name: synthetic ids are plain integers "
+                         "without one; run without it")
     try:
         class_weights = parse_class_weights(args.class_weights, args.num_classes)
     except ValueError as e:
@@ -400,15 +450,32 @@ def main(argv=None):
                                   grayscale_p=photo["grayscale"], erase_p=photo["erase"], norm=(mean, std, rescale))
         else:
             augmenter = Augmenter(S, args.aug_crop_scale, args.aug_flip, seed=args.seed, rank=rank)
+    text_augmenter = None
+    if (token_aug or args.aug_whole_word) and args.only_test:
+        logger.info("%s / --aug_whole_word are ignored with --only_test: only training batches are augmented", _TOKEN_NAMES)
+    elif token_aug:
+        # a generator of its own, seeded from (--seed, rank), as the image augmenter's
+        from .text_augment import TokenAugmenter
+        if args.data_path is None:
+            settings = dict(SYNTHETIC_TOKENS, vocab=int(text_config.vocab_size))
+        else:
+            settings = token_settings(train_dl.dataset.tokenizer, args.aug_whole_word, args.aug_token_mask > 0.0)
+        try:
+            text_augmenter = TokenAugmenter(*token_p, seed=args.seed, rank=rank, **settings)
+        except ValueError as e:
+            raise SystemExit(f"{_TOKEN_NAMES}: {e}")
+    elif args.aug_whole_word:
+        logger.info("--aug_whole_word has no effect without %s", _TOKEN_NAMES)
     if args.cache_dataset == "device" and args.only_test:
         logger.info("--cache_dataset device is ignored with --only_test: a single pass over the test split gains nothing")
     elif args.cache_dataset == "device":
         # every rank caches the whole of each split (the training shards change every epoch); the default generator is untouched
         from .cache import cache_loaders
+        more = {} if text_augmenter is None else {"text_augmenters": {"train": text_augmenter}}
         cached = cache_loaders({"train": train_dl, "dev": dev_dl, "test": test_dl}, args.device, logger,
-                               augmenters={"train": augmenter} if augmenter is not None else None)
+                               augmenters={"train": augmenter} if augmenter is not None else None, **more)
         train_dl, dev_dl, test_dl = cached["train"], cached["dev"], cached["test"]
-        augmenter = None  # the cached training loader augments its own batches
+        augmenter = text_augmenter = None  # the cached training loader augments its own batches
     if args.ema_decay and args.only_test:
         logger.info("--ema_decay is ignored with --only_test: the checkpoint already holds the weights that were saved")
         args.ema_decay = 0.0
@@ -433,8 +500,9 @@ def main(argv=None):
         trainer._load_checkpoint(args.load_path)  # strict: every key of the model, nothing else
         trainer.predict(test_dl, args.write_path)
         return
+    more = {} if text_augmenter is None else {"text_augmenter": text_augmenter}
     trainer = MSDTrainer(train_data=train_dl, dev_data=dev_dl, test_data=test_dl, model=model, args=args, logger=logger,
-                         writer=None, augmenter=augmenter)
+                         writer=None, augmenter=augmenter, **more)
     trainer.train(clip_sd, bert_sd)  # None, None without --pretrained: randomly initialised encoders
     if trainer.samples_per_sec:
         logger.info("training throughput: %.1f samples/s on %d GPU(s)", trainer.samples_per_sec, world)

@@ -16,6 +16,8 @@ state-dict key names (:210-216).  Differences, all deliberate (SURVEY.md Appendi
   * optional image augmentation of the TRAINING batches (``augmenter``, d2r_amd.augment: random resized crop and flip, colour
     jitter, random grayscale and random erasing on the device; a CachedLoader carries its own); evaluate() / test() / predict()
     never augment;
+  * optional text augmentation of the TRAINING batches (``text_augmenter``, d2r_amd.text_augment: token deletion, [MASK] and
+    random-id replacement in one launch on the device; a CachedLoader carries its own), under the same rules;
   * evaluate() / test() count a confusion matrix on the device (d2r_confusion_add) instead of copying labels and predictions to
     the host per batch, and log per-class precision / recall / F1 / support after the four aggregates; they return the scalar
     entries as before, the whole result (with "confusion" and "per_class") stays in last_dev_result / last_test_result.
@@ -136,9 +138,10 @@ def ingest_pretrained(model, clip_model_dict, bert_model_dict):
 
 class MSDTrainer:
     def __init__(self, train_data=None, dev_data=None, test_data=None, model=None, args=None, logger=None,
-                 writer=None, augmenter=None) -> None:
+                 writer=None, augmenter=None, *, text_augmenter=None) -> None:
         self.train_data, self.dev_data, self.test_data = train_data, dev_data, test_data
         self.augmenter = augmenter  # training batches of packed images only (a CachedLoader augments its own batches)
+        self.text_augmenter = text_augmenter  # training batches' token tensors (a CachedLoader with its own: None here)
         self.model, self.args = model, args
         self.logger = logger or logging.getLogger(__name__)
         self.writer = writer
@@ -193,13 +196,17 @@ class MSDTrainer:
         self.store.refresh_lowp()
         self.logger.info("Load model successful!")
 
-    def _to_device(self, batch, augmenter=None):
+    def _to_device(self, batch, augmenter=None, text_augmenter=None):
         # tensors are copied; a packed batch of images (MSDDataset + ClipCollate: PackedImages, or PackedJpegImages with
-        # image_decode="device") becomes its CLIP pixel values on the device - through `augmenter` when the training loop passes one
+        # image_decode="device") becomes its CLIP pixel values on the device - through `augmenter` when the training loop passes one;
+        # the three token tensors go through `text_augmenter` once they are there, when the training loop passes one
         def pixel_values(t):
             return t.to_pixel_values(self.args.device) if augmenter is None else augmenter.apply_packed(t, self.args.device)
-        return tuple(t.to(self.args.device, non_blocking=True) if isinstance(t, torch.Tensor) else
-                     pixel_values(t) if hasattr(t, "to_pixel_values") else t for t in batch)
+        moved = tuple(t.to(self.args.device, non_blocking=True) if isinstance(t, torch.Tensor) else
+                      pixel_values(t) if hasattr(t, "to_pixel_values") else t for t in batch)
+        if text_augmenter is None:
+            return moved
+        return (*text_augmenter.apply_batch(*moved[:3]), *moved[3:])
 
     # -- training (modules/train.py:77-159) -----------------------------------------------------------
     def train(self, clip_model_dict=None, bert_model_dict=None):
@@ -232,6 +239,9 @@ class MSDTrainer:
         augmenter = self.augmenter or getattr(self.train_data, "augmenter", None)
         if augmenter is not None:
             self.logger.info("  Image augmentation of the training batches: %s", augmenter.describe())
+        text_augmenter = self.text_augmenter or getattr(self.train_data, "text_augmenter", None)
+        if text_augmenter is not None:
+            self.logger.info("  Text augmentation of the training batches: %s", text_augmenter.describe())
         run_loss = torch.zeros((), dtype=torch.float32, device=self.args.device)
         clipping = self.optimizer.max_grad_norm is not None
         grad_norm = torch.zeros((), dtype=torch.float32, pin_memory=torch.cuda.is_available()) if clipping else None
@@ -249,7 +259,7 @@ class MSDTrainer:
                 self.step += 1
                 if self.step == warm + 1 and t_mark is None:
                     t_mark = time.time()
-                packed, batch = batch, self._to_device(batch, self.augmenter)
+                packed, batch = batch, self._to_device(batch, self.augmenter, self.text_augmenter)
                 self.decode_log.note(packed)
                 self.dp.begin_step()
                 (loss, logits), labels = self._step(batch, mode="train")

@@ -726,6 +726,41 @@ int d2r_clip_cache_augment_photo(const uint8_t* cache, int64_t cache_rows, const
                                  const d2r_clip_augment_desc* h_aug, const d2r_clip_augment_desc* aug,
                                  const d2r_clip_photo_desc* h_photo, const d2r_clip_photo_desc* photo, int B, int S, const float* h_norm,
                                  float rescale, float* out, void* ws, size_t ws_bytes, void* stream);
+/* K23  Text augmentation on the token rows (d2r_amd/text_augment.py, --aug_token_delete / --aug_token_mask / --aug_token_replace /
+ * --aug_whole_word).  d2r_token_augment builds the three token tensors of a batch from their source rows - what three d2r_gather_rows
+ * calls do - and deletes, masks or replaces tokens per sample on the way.
+ *   ids, mask, seg : int64 [rows, L] on the device (the cache's tensors, or the batch's own);
+ *   idx / h_idx    : the B source rows (int64 [B] on the device) and their host copy;
+ *   plan / h_plan  : uint32 [B, L] on the device and its host copy, one word per output sample and SOURCE position: bits 0-1 the op
+ *                    (0 keep, 1 delete, 2 mask, 3 replace), bits 2-31 the replacement id;
+ *   cont           : uint8 [vocab] on the device, 1 where an id is a continuation piece of a word ("##..."), or NULL;
+ *   out_ids, out_mask, out_seg : int64 [B, L], OVERWRITTEN.
+ * For output sample b with source row r = idx[b]:
+ *   - real tokens: n = the number of non-zero entries of mask[r]; the real tokens are the positions 0..n-1 (a mask that is not a
+ *     prefix of ones is outside the contract; whatever it is, nothing outside the rows is read or written);
+ *   - content positions: 0 ([CLS]) and n-1 ([SEP]) are never touched; the content positions are 1 <= l <= n-2, none when n <= 2 (the
+ *     row then comes out unchanged);
+ *   - word heads: l is a head if l == 1, or cont == NULL, or ids[r][l] lies outside [0, vocab) (the table is never read out of
+ *     range); otherwise exactly when cont[ids[r][l]] == 0;
+ *   - effective op: w(l) = the largest head <= l; the effective op of l is the op of plan[b][w(l)], so a word's pieces share their
+ *     head's fate.  With cont == NULL every position is its own word;
+ *   - keep-one rule: if the effective op of EVERY content position is delete, none is deleted: they are all kept, a post never
+ *     becomes [CLS] [SEP].  Applied after the word propagation (mask and replace cannot occur in such a row);
+ *   - value at a surviving content position: keep ids[r][l], mask mask_id, replace plan[b][l] >> 2 - the position's OWN replacement
+ *     id, even when the op came from its head;
+ *   - output layout: [CLS], the surviving content tokens in their order, [SEP] at positions 0..n'-1 of out_ids[b]; out_seg[b][j] is
+ *     the seg value of the source position that landed at j, out_mask[b][j] = 1; positions n'..L-1 get pad_id, 0 and 0.
+ * With an all-zero plan the three outputs are bit for bit what d2r_gather_rows gives for the three tensors, for rows whose padding is
+ * pad_id / 0 / 0 and whose mask is a prefix of ones (what the data layer writes).  Integer work only: a second run gives the same bits.
+ * Checked on the host copies before anything is enqueued (a refused call writes nothing): a null pointer other than cont, B outside
+ * [1, 65535], L outside [2, 1024], rows < 1, an h_idx outside [0, rows), vocab < 1, mask_id or pad_id outside [0, vocab), a plan word
+ * whose replacement id is >= vocab (with op 3, or with any other op: a continuation piece takes its head's op and its own id), int64
+ * pointers that are not 8-byte or plan pointers that are not 4-byte aligned, an output range that overlaps an input tensor or
+ * another output. */
+int d2r_token_augment(const int64_t* ids, const int64_t* mask, const int64_t* seg, int64_t rows, int L, const int64_t* h_idx,
+                      const int64_t* idx, const uint32_t* h_plan, const uint32_t* plan, int B, const uint8_t* cont /* or NULL */,
+                      int64_t vocab, int64_t mask_id, int64_t pad_id, int64_t* out_ids, int64_t* out_mask, int64_t* out_seg,
+                      void* stream);
 /* K19  Baseline JPEG decoding of a batch of images on the device (processor/dataset.py:89: Image.open(p).convert("RGB") in the
  * reference's loader workers), bit-identical to libjpeg-turbo's default path as Pillow uses it: Huffman decoding, ISLOW IDCT with
  * its range-limit table, fancy h2v1 / h2v2 chroma upsampling, fixed-point YCbCr -> RGB.  The host (d2r_amd/jpeg.py) parses the
