@@ -83,6 +83,10 @@ class HeadDesc(C.Structure):
                 ("scratch_bytes", sz), ("d_logits", vp), ("d_pooled", vp), ("class_weight", vp), ("label_smoothing", f32)]
 
 
+class HeadMixDesc(C.Structure):  # d2r_head_mix_desc: the head's descriptor, then the second labels and the first label's share
+    _fields_ = [("head", HeadDesc), ("labels_b", vp), ("mix_lam", vp)]
+
+
 class ClipImageDesc(C.Structure):
     _fields_ = [("src_offset", i64)] + [(n, i32) for n in ("H", "W", "rh", "rw", "top", "left", "kx", "ky", "bx", "cx", "by", "cy",
                                                           "row0", "nrows")] + [("ws_offset", i64)]
@@ -117,6 +121,8 @@ SIGNATURES = {
     "d2r_head_bwd_scratch": (sz, [i32, i32, i32, i32, i32, i32]),
     "d2r_head_fwd": (i32, [C.POINTER(HeadDesc), vp]),
     "d2r_head_bwd": (i32, [C.POINTER(HeadDesc), vp]),
+    "d2r_head_mix_fwd": (i32, [C.POINTER(HeadMixDesc), vp]),
+    "d2r_head_mix_bwd": (i32, [C.POINTER(HeadMixDesc), vp]),
     "d2r_version": (C.c_char_p, []),
     "d2r_last_error": (C.c_char_p, []),
     "d2r_gemm": (i32, [C.POINTER(GemmDesc), vp]),
@@ -196,6 +202,8 @@ SIGNATURES = {
     "d2r_ce_bwd": (i32, [vp, vp, i32, i32, vp, vp, vp]),
     "d2r_ce_fwd_ex": (i32, [vp, vp, vp, f32, i32, i32, vp, vp]),
     "d2r_ce_bwd_ex": (i32, [vp, vp, vp, f32, i32, i32, vp, vp, vp]),
+    "d2r_ce_mix_fwd": (i32, [vp, vp, vp, vp, vp, f32, i32, i32, vp, vp]),
+    "d2r_ce_mix_bwd": (i32, [vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp]),
     "d2r_argmax_rows": (i32, [vp, i64, i64, i32, vp, vp]),
     "d2r_confusion_add": (i32, [vp, i64, vp, i64, i32, vp, vp]),
     "d2r_block_merge_fwd": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
@@ -213,6 +221,7 @@ SIGNATURES = {
     "d2r_clip_cache_augment_photo_ws_bytes": (sz, [i32, i32]),
     "d2r_clip_cache_augment_photo": (i32, [vp, i64, vp, vp, C.POINTER(ClipAugmentDesc), vp, C.POINTER(ClipPhotoDesc), vp, i32, i32,
                                            C.POINTER(f32), f32, vp, vp, sz, vp]),
+    "d2r_image_mix": (i32, [vp, vp, i32, i32, vp, vp, vp]),
     "d2r_token_augment": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp, i32, vp, i64, i64, i64, vp, vp, vp, vp]),
     "d2r_jpeg_decode_ws_bytes": (sz, [C.POINTER(JpegImageDesc), i32]),
     "d2r_jpeg_decode": (i32, [vp, i64, C.POINTER(JpegImageDesc), vp, i32, C.POINTER(JpegSegment), vp, i32, vp, vp, i64,

@@ -14,10 +14,13 @@
 // a per-sample box of the crop resampled bilinearly to S x S and an optional mirror (d2r_amd/augment.py: random resized crop, flip).
 // d2r_clip_cache_augment_photo resamples the raw values instead of the table's and applies brightness, contrast, saturation, hue,
 // grayscale, the normalisation and an erase box per sample (K22: colour jitter, random grayscale, random erasing).
+// d2r_image_mix (K24) runs after all of them, on the finished fp32 batch: every sample is blended with, or gets a box pasted from,
+// another sample of the batch (d2r_amd/mix.py: MixUp, CutMix).
 #include "common.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 namespace {
@@ -359,6 +362,53 @@ __global__ __launch_bounds__(PHOTO_BLOCK) void clip_photo_apply_kernel(const uin
   }
 }
 
+// ---- K24: MixUp / CutMix of a finished pixel batch ----
+
+// one component: the partner's value inside the box, the sample's own where a == 1, the blend otherwise
+__device__ __forceinline__ float mix_pick(float own, float other, float a, bool boxed) {
+#pragma clang fp contract(off)
+  return boxed ? other : (a == 1.0f ? own : a * own + (1.0f - a) * other);
+}
+
+// out[b] = in[b] mixed with in[partner_b] (desc[b] = {partner, bits of a, x0, y0, w, h, 0, 0}): four consecutive columns of one row
+// per thread, as in clip_cache_augment_kernel.  VEC (S a multiple of 4, in and out 16-byte aligned): one float4 load per input and
+// one float4 store; a box edge inside the quad is a select per component.  The partner is read only where a != 1 or the row crosses
+// the box, so an untouched sample costs one read and one write.
+template <bool VEC>
+__global__ __launch_bounds__(256) void image_mix_kernel(const float* __restrict__ in, float* __restrict__ out, int S, int quads,
+                                                        const int32_t* __restrict__ desc) {
+  const int32_t* d = desc + (int64_t)blockIdx.y * 8;  // uniform: scalar loads
+  const int partner = d[0], x0 = d[2], y0 = d[3], x1 = d[2] + d[4], y1 = d[3] + d[5];
+  const float a = __int_as_float(d[1]);
+  const int t = blockIdx.x * 256 + threadIdx.x;  // < 3 * 4096 * 1024
+  if (t >= 3 * S * quads) return;
+  const int line = t / quads, j0 = (t - line * quads) * 4;
+  const int i = line % S;
+  const int64_t sample = (int64_t)3 * S * S, off = (int64_t)line * S + j0;
+  const float* own = in + (int64_t)blockIdx.y * sample + off;
+  const float* other = in + (int64_t)partner * sample + off;
+  float* o = out + (int64_t)blockIdx.y * sample + off;
+  const bool row_boxed = i >= y0 && i < y1 && x0 < x1;
+  const bool need_other = a != 1.0f || (row_boxed && j0 < x1 && j0 + 4 > x0);
+  if (VEC) {
+    const float4 p = *reinterpret_cast<const float4*>(own);
+    const float4 q = need_other ? *reinterpret_cast<const float4*>(other) : p;
+    float4 r;
+    r.x = mix_pick(p.x, q.x, a, row_boxed && j0 >= x0 && j0 < x1);
+    r.y = mix_pick(p.y, q.y, a, row_boxed && j0 + 1 >= x0 && j0 + 1 < x1);
+    r.z = mix_pick(p.z, q.z, a, row_boxed && j0 + 2 >= x0 && j0 + 2 < x1);
+    r.w = mix_pick(p.w, q.w, a, row_boxed && j0 + 3 >= x0 && j0 + 3 < x1);
+    *reinterpret_cast<float4*>(o) = r;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (j0 + k < S) {
+        const float p = own[k];
+        o[k] = mix_pick(p, need_other ? other[k] : p, a, row_boxed && j0 + k >= x0 && j0 + k < x1);
+      }
+  }
+}
+
 // dst[b] = src[idx[b]], rows of `elems` V-sized pieces
 template <typename V>
 __global__ __launch_bounds__(256) void gather_rows_kernel(V* __restrict__ dst, const V* __restrict__ src, int64_t elems,
@@ -582,6 +632,33 @@ extern "C" int d2r_clip_cache_augment_photo(const uint8_t* cache, int64_t cache_
   hipLaunchKernelGGL(clip_photo_apply_kernel, dim3(parts, B), dim3(PHOTO_BLOCK), 0, st, cache, row_bytes, idx, aug, photo, S, quads,
                      rescale, nm, (const float*)ws, parts, out);
   return d2r_check_launch("d2r_clip_cache_augment_photo");
+}
+
+extern "C" int d2r_image_mix(const float* in, float* out, int B, int S, const int32_t* h_desc, const int32_t* desc, void* stream) {
+  const char* who = "d2r_image_mix";
+  D2R_REQUIRE(in && out && h_desc && desc, "%s: null pointer", who);
+  D2R_REQUIRE(B >= 1 && B <= 65535 && S >= 1 && S <= 4096, "%s: bad batch %d or crop size %d", who, B, S);
+  const uintptr_t pi = reinterpret_cast<uintptr_t>(in), po = reinterpret_cast<uintptr_t>(out);
+  D2R_REQUIRE(((pi | po | reinterpret_cast<uintptr_t>(desc)) & 3u) == 0, "%s: in / out / desc must be 4-byte aligned", who);
+  const uintptr_t bytes = (uintptr_t)B * 3 * S * S * sizeof(float);
+  D2R_REQUIRE(po >= pi + bytes || pi >= po + bytes, "%s: out overlaps in (sample b reads its partner: the call cannot run in place)", who);
+  for (int b = 0; b < B; ++b) {
+    const int32_t* d = h_desc + (size_t)b * 8;
+    float a;
+    std::memcpy(&a, d + 1, sizeof a);
+    D2R_REQUIRE(d[0] >= 0 && d[0] < B, "%s: sample %d: partner is %d, outside the %d samples", who, b, d[0], B);
+    D2R_REQUIRE(std::isfinite(a) && a >= 0.0f && a <= 1.0f, "%s: sample %d: a is %g, not a finite value in [0, 1]", who, b, (double)a);
+    D2R_REQUIRE(d[4] >= 0 && d[5] >= 0, "%s: sample %d: w is %d and h is %d, negative", who, b, d[4], d[5]);
+    D2R_REQUIRE(d[2] >= 0 && d[3] >= 0 && d[4] <= S && d[5] <= S && d[2] <= S - d[4] && d[3] <= S - d[5],
+                "%s: sample %d: the %d x %d box at (%d, %d) does not lie inside [0, %d] x [0, %d]", who, b, d[4], d[5], d[2], d[3], S, S);
+  }
+  const int quads = (S + 3) / 4;
+  const dim3 grid(d2r_cdiv((int64_t)3 * S * quads, 256), B);
+  if ((S & 3) == 0 && ((pi | po) & 15u) == 0)
+    hipLaunchKernelGGL(image_mix_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, in, out, S, quads, desc);
+  else
+    hipLaunchKernelGGL(image_mix_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, in, out, S, quads, desc);
+  return d2r_check_launch("d2r_image_mix");
 }
 
 extern "C" int d2r_gather_rows(void* dst, const void* src, int64_t src_rows, int64_t row_bytes, const int64_t* h_idx, const int64_t* idx,

@@ -941,7 +941,8 @@ extern "C" size_t d2r_head_bwd_scratch(int B, int E, int mm, int chunks, int ran
   return Z.off;
 }
 
-extern "C" int d2r_head_fwd(const d2r_head_desc* D, void* stream) {
+// labels_b / mix_lam: the two fields of d2r_head_mix_desc (NULL from d2r_head_fwd / d2r_head_bwd)
+static int head_fwd(const d2r_head_desc* D, const int64_t* labels_b, const float* mix_lam, void* stream) {
   HeadDims h;
   TRY(head_dims(D, h));
   D2R_REQUIRE(D->x0 && D->x1 && D->logits && D->pooled && D->arena, "d2r_head_fwd: null pointer");
@@ -959,7 +960,9 @@ extern "C" int d2r_head_fwd(const d2r_head_desc* D, void* stream) {
   TRY(lin(c, h.B, h.E, h.mm, a.z, h.mm, D->lin_out, D->pooled));
   TRY(lin(c, h.B, h.classes, h.E, D->pooled, h.E, D->fc, D->logits));
   if (!D->labels) return D2R_OK;  // prediction: logits and pooled only
-  if (D->class_weight || D->label_smoothing != 0.f)
+  if (labels_b || mix_lam)  // MixUp / CutMix: two labels per row (one of the two alone is refused there)
+    TRY(d2r_ce_mix_fwd(D->logits, D->labels, labels_b, mix_lam, D->class_weight, D->label_smoothing, h.B, h.classes, a.ce, stream));
+  else if (D->class_weight || D->label_smoothing != 0.f)
     TRY(d2r_ce_fwd_ex(D->logits, D->labels, D->class_weight, D->label_smoothing, h.B, h.classes, a.ce, stream));
   else
     TRY(d2r_ce_fwd(D->logits, D->labels, h.B, h.classes, a.ce, stream));
@@ -968,7 +971,7 @@ extern "C" int d2r_head_fwd(const d2r_head_desc* D, void* stream) {
   return d2r_lincomb(xs, coef, 2, D->loss, stream);
 }
 
-extern "C" int d2r_head_bwd(const d2r_head_desc* D, void* stream) {
+static int head_bwd(const d2r_head_desc* D, const int64_t* labels_b, const float* mix_lam, void* stream) {
   HeadDims h;
   TRY(head_dims(D, h));
   D2R_REQUIRE(D->labels, "d2r_head_bwd: labels are required (a label-free forward has no loss to differentiate)");
@@ -984,7 +987,10 @@ extern "C" int d2r_head_bwd(const d2r_head_desc* D, void* stream) {
   head_plan(A, h, a);
   head_plan_bwd(Z, h, g);
   TRY(d2r_axpby(D2R_F32, 1.f, D->d_loss, 0.f, D->d_js, 1, stream));  // loss = ce + js
-  if (D->class_weight || D->label_smoothing != 0.f)
+  if (labels_b || mix_lam)
+    TRY(d2r_ce_mix_bwd(D->logits, D->labels, labels_b, mix_lam, D->class_weight, D->label_smoothing, h.B, h.classes, D->d_loss,
+                       g.dlogits, stream));
+  else if (D->class_weight || D->label_smoothing != 0.f)
     TRY(d2r_ce_bwd_ex(D->logits, D->labels, D->class_weight, D->label_smoothing, h.B, h.classes, D->d_loss, g.dlogits, stream));
   else
     TRY(d2r_ce_bwd(D->logits, D->labels, h.B, h.classes, D->d_loss, g.dlogits, stream));
@@ -1001,5 +1007,16 @@ extern "C" int d2r_head_bwd(const d2r_head_desc* D, void* stream) {
   TRY(dwg(c, h.B, h.mm, h.E, g.dh0, h.mm, D->x0, h.E, D->lin0));
   TRY(dxg(c, h.B, h.E, h.mm, g.dh1, h.mm, D->lin1.w, D->d_x1, h.E));
   return dwg(c, h.B, h.mm, h.E, g.dh1, h.mm, D->x1, h.E, D->lin1);
+}
+
+extern "C" int d2r_head_fwd(const d2r_head_desc* D, void* stream) { return head_fwd(D, nullptr, nullptr, stream); }
+extern "C" int d2r_head_bwd(const d2r_head_desc* D, void* stream) { return head_bwd(D, nullptr, nullptr, stream); }
+extern "C" int d2r_head_mix_fwd(const d2r_head_mix_desc* D, void* stream) {
+  D2R_REQUIRE(D, "d2r_head_mix_fwd: null descriptor");
+  return head_fwd(&D->head, D->labels_b, D->mix_lam, stream);
+}
+extern "C" int d2r_head_mix_bwd(const d2r_head_mix_desc* D, void* stream) {
+  D2R_REQUIRE(D, "d2r_head_mix_bwd: null descriptor");
+  return head_bwd(&D->head, D->labels_b, D->mix_lam, stream);
 }
 

@@ -480,6 +480,126 @@ extern "C" int d2r_ce_bwd_ex(const float* logits, const int64_t* labels, const f
   return d2r_check_launch("d2r_ce_bwd_ex");
 }
 
+// Mixed-label cross entropy (MixUp / CutMix): the formulas of the _ex kernels with the one-hot target replaced by
+// lam_b onehot(y_b) + (1 - lam_b) onehot(y2_b):
+//   hard_b(c) = (1-e) (lam_b w[y_b] [c == y_b] + (1 - lam_b) w[y2_b] [c == y2_b])
+//   loss = sum_b [ sum_c hard_b(c) (-lp[b,c]) + (e/C) sum_c w[c] (-lp[b,c]) ] / W,   W = sum_b (lam_b w[y_b] + (1 - lam_b) w[y2_b])
+// The same launch shapes, per-row max / sum-of-exponentials and fixed-order block_sum as the kernels above.  Contraction is off and
+// every fused multiply-add is written out, in the order the kernels above are compiled to, so that a row with lam == 1 goes through
+// the very operations of ce_*_kernel (PLAIN: no class weights, no smoothing) or ce_*_ex_kernel and gives their bits; the partner's
+// terms are then +-0.  Without class weights W is B exactly (lam + (1 - lam) need not round to 1).
+template <bool PLAIN>
+__global__ __launch_bounds__(256) void ce_mix_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                         const int64_t* __restrict__ labels_b, const float* __restrict__ lam,
+                                                         const float* __restrict__ cw, float eps, int B, int C,
+                                                         float* __restrict__ loss) {
+#pragma clang fp contract(off)
+  __shared__ float sh[16];
+  const float e_c = eps / (float)C;
+  float acc = 0.f, wacc = 0.f;
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const float* x = logits + (int64_t)b * C;
+    float m = -INFINITY;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, x[c]);
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s += expf(x[c] - m);
+    const float lse = m + logf(s);
+    const int64_t y = labels[b], y2 = labels_b[b];
+    const float l1 = lam[b], l2 = 1.f - l1;
+    const float d1 = lse - x[y], d2 = lse - x[y2];
+    if (PLAIN) {
+      acc += fmaf(l2, d2, l1 * d1);
+    } else {
+      const float wy = cw ? cw[y] : 1.f, wy2 = cw ? cw[y2] : 1.f;
+      float sm = 0.f;  // sum_c w[c] (-lp[b,c])
+      for (int c = 0; c < C; ++c) sm = fmaf(cw ? cw[c] : 1.f, lse - x[c], sm);
+      const float h1 = (1.f - eps) * wy * l1, h2 = (1.f - eps) * wy2 * l2;
+      acc += fmaf(h2, d2, fmaf(e_c, sm, h1 * d1));
+      wacc += fmaf(l2, wy2, l1 * wy);
+    }
+  }
+  const float t = block_sum(acc, sh);
+  const float wsum = (!PLAIN && cw) ? block_sum(wacc, sh) : (float)B;
+  if (threadIdx.x == 0) loss[0] = t / wsum;
+}
+// dlogits[b,c] = dloss / W * ( p[b,c] (sum_k hard_b(k) + (e/C) sum_k w[k]) - hard_b(c) - (e/C) w[c] ); W is summed again by every
+// workgroup, as in ce_bwd_ex_kernel.
+template <bool PLAIN>
+__global__ __launch_bounds__(256) void ce_mix_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                         const int64_t* __restrict__ labels_b, const float* __restrict__ lam,
+                                                         const float* __restrict__ cw, float eps, int B, int C,
+                                                         const float* __restrict__ dloss, float* __restrict__ dlogits) {
+#pragma clang fp contract(off)
+  __shared__ float sh[16];
+  float wsum = (float)B, wall = (float)C;  // W, sum_k w[k]
+  if (!PLAIN && cw) {
+    float wacc = 0.f;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+      const float l1 = lam[b];
+      wacc += fmaf(1.f - l1, cw[labels_b[b]], l1 * cw[labels[b]]);
+    }
+    wsum = block_sum(wacc, sh);
+    wall = 0.f;
+    for (int c = 0; c < C; ++c) wall += cw[c];
+  }
+  const float sc = dloss[0] / wsum;
+  const float e_c = eps / (float)C;
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
+    const float* x = logits + (int64_t)b * C;
+    float m = -INFINITY;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, x[c]);
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s += expf(x[c] - m);
+    const float inv = 1.f / s;
+    const int64_t y = labels[b], y2 = labels_b[b];
+    const float l1 = lam[b], l2 = 1.f - l1;
+    if (PLAIN) {
+      for (int c = 0; c < C; ++c) {
+        const float t = fmaf(expf(x[c] - m), inv, -(c == y ? l1 : 0.f)) - (c == y2 ? l2 : 0.f);
+        dlogits[(int64_t)b * C + c] = sc * t;
+      }
+    } else {
+      const float wy = cw ? cw[y] : 1.f, wy2 = cw ? cw[y2] : 1.f;
+      const float h1 = (1.f - eps) * wy * l1, h2 = (1.f - eps) * wy2 * l2;
+      const float mass = fmaf(1.f - eps, fmaf(l2, wy2, l1 * wy), e_c * wall);
+      for (int c = 0; c < C; ++c) {
+        float t = fmaf(mass, expf(x[c] - m) * inv, -(c == y ? h1 : 0.f)) - (c == y2 ? h2 : 0.f);
+        t = fmaf(-e_c, cw ? cw[c] : 1.f, t);
+        dlogits[(int64_t)b * C + c] = sc * t;
+      }
+    }
+  }
+}
+extern "C" int d2r_ce_mix_fwd(const float* logits, const int64_t* labels, const int64_t* labels_b, const float* lam,
+                              const float* class_weight, float label_smoothing, int B, int C, float* loss, void* stream) {
+  D2R_REQUIRE(!labels_b == !lam, "d2r_ce_mix_fwd: labels_b and lam must both be given or both be NULL");
+  if (!labels_b) return d2r_ce_fwd_ex(logits, labels, class_weight, label_smoothing, B, C, loss, stream);  // today's kernels, bit for bit
+  D2R_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "d2r_ce_mix_fwd: label_smoothing %g is outside [0, 1)", (double)label_smoothing);
+  D2R_REQUIRE(logits && labels && loss && B >= 1 && C >= 1, "d2r_ce_mix_fwd: bad arguments");
+  if (!class_weight && label_smoothing == 0.f)
+    hipLaunchKernelGGL(ce_mix_fwd_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, labels_b, lam, class_weight,
+                       label_smoothing, B, C, loss);
+  else
+    hipLaunchKernelGGL(ce_mix_fwd_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, labels_b, lam, class_weight,
+                       label_smoothing, B, C, loss);
+  return d2r_check_launch("d2r_ce_mix_fwd");
+}
+extern "C" int d2r_ce_mix_bwd(const float* logits, const int64_t* labels, const int64_t* labels_b, const float* lam,
+                              const float* class_weight, float label_smoothing, int B, int C, const float* dloss, float* dlogits,
+                              void* stream) {
+  D2R_REQUIRE(!labels_b == !lam, "d2r_ce_mix_bwd: labels_b and lam must both be given or both be NULL");
+  if (!labels_b) return d2r_ce_bwd_ex(logits, labels, class_weight, label_smoothing, B, C, dloss, dlogits, stream);
+  D2R_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "d2r_ce_mix_bwd: label_smoothing %g is outside [0, 1)", (double)label_smoothing);
+  D2R_REQUIRE(logits && labels && dloss && dlogits && B >= 1 && C >= 1, "d2r_ce_mix_bwd: bad arguments");
+  if (!class_weight && label_smoothing == 0.f)
+    hipLaunchKernelGGL(ce_mix_bwd_kernel<true>, dim3(d2r_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, labels, labels_b, lam,
+                       class_weight, label_smoothing, B, C, dloss, dlogits);
+  else
+    hipLaunchKernelGGL(ce_mix_bwd_kernel<false>, dim3(d2r_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, labels, labels_b, lam,
+                       class_weight, label_smoothing, B, C, dloss, dlogits);
+  return d2r_check_launch("d2r_ce_mix_bwd");
+}
+
 // =====================================================================================================
 // argmax over the last dim (logits.argmax(-1) at modules/train.py:181,243): thread per row, torch.argmax's rules
 // =====================================================================================================

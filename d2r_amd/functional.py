@@ -1226,13 +1226,35 @@ def _loss_options(weight, label_smoothing, classes, device, what):
     return weight, eps
 
 
-def _head_fwd(x0, x1, js, labels, bundle: HeadBundle, weight=None, label_smoothing=0.0):
+def _mix_options(labels, labels_b, lam, what):
+    """(int64 [B], fp32 [B]) contiguous on the labels' device, or (None, None): the second labels and the first label's share of a
+    MixUp / CutMix batch.  Both or neither."""
+    if labels_b is None and lam is None:
+        return None, None
+    if labels_b is None or lam is None:
+        raise _lib.D2RError(f"{what}: labels_b and lam go together, got only one of them")
+    if labels is None:
+        raise _lib.D2RError(f"{what}: labels_b / lam were given without labels")
+    if labels_b.numel() != labels.numel() or lam.numel() != labels.numel() or lam.dtype != torch.float32 or labels_b.is_floating_point() \
+            or labels_b.device != labels.device or lam.device != labels.device:
+        raise _lib.D2RError(f"{what}: labels_b must be an integer and lam an fp32 tensor with one entry per label ({labels.numel()}) on "
+                            f"{labels.device}")
+    return labels_b.contiguous().long(), lam.contiguous()
+
+
+def _head_fwd(x0, x1, js, labels, bundle: HeadBundle, weight=None, label_smoothing=0.0, labels_b=None, lam=None):
     """One d2r_head_fwd call on contiguous fp32 inputs: -> (loss, logits, pooled, descriptor, arena).  labels=None: the label-free
     forward (labels, js and loss NULL; loss returned as None) - the same descriptor and launches up to the logits otherwise.
-    weight / label_smoothing: the descriptor's class_weight / label_smoothing (the caller keeps `weight` alive)."""
+    weight / label_smoothing: the descriptor's class_weight / label_smoothing (the caller keeps `weight` alive).
+    labels_b / lam (both or neither; kept alive by the caller): d2r_head_mix_fwd on a d2r_head_mix_desc, which is returned in the
+    descriptor's place (its `head` field is the descriptor)."""
     B = x0.shape[0]
     lib = _lib.load()
-    d = _lib.HeadDesc()
+    md = None
+    if labels_b is not None:
+        md = _lib.HeadMixDesc()
+        md.labels_b, md.mix_lam = labels_b.data_ptr(), lam.data_ptr()
+    d = _lib.HeadDesc() if md is None else md.head
     d.B, d.E, d.mm, d.chunks, d.rank, d.classes = B, bundle.E, bundle.mm, bundle.chunks, bundle.rank, bundle.classes
     d.lin0, d.lin1, d.merge0, d.merge1, d.lin_out, d.fc = bundle.lp
     loss = None if labels is None else torch.empty((), dtype=torch.float32, device=x0.device)
@@ -1245,8 +1267,11 @@ def _head_fwd(x0, x1, js, labels, bundle: HeadBundle, weight=None, label_smoothi
     d.loss, d.logits, d.pooled = _ptr(loss), logits.data_ptr(), pooled.data_ptr()
     d.arena, d.arena_bytes, d.splitk_ws, d.splitk_bytes = arena.data_ptr(), arena.numel(), ws.data_ptr(), ws.numel()
     d.class_weight, d.label_smoothing = _ptr(weight), label_smoothing
-    _lib.call("d2r_head_fwd", C.byref(d), _stream(), meta=dict(group="head_fwd"))
-    return loss, logits, pooled, d, arena
+    if md is None:
+        _lib.call("d2r_head_fwd", C.byref(d), _stream(), meta=dict(group="head_fwd"))
+    else:
+        _lib.call("d2r_head_mix_fwd", C.byref(md), _stream(), meta=dict(group="head_fwd"))
+    return loss, logits, pooled, d if md is None else md, arena
 
 
 class _Head(torch.autograd.Function):
@@ -1254,12 +1279,13 @@ class _Head(torch.autograd.Function):
     gradient (the end of the training graph); a gradient arriving at logits / pooled is refused."""
 
     @staticmethod
-    def forward(ctx, x0, x1, js, labels, anchor, bundle, weight, label_smoothing):
+    def forward(ctx, x0, x1, js, labels, anchor, bundle, weight, label_smoothing, labels_b=None, lam=None):
         x0, x1, js = x0.contiguous(), x1.contiguous(), js.contiguous()
         labels = labels.contiguous().long()
-        loss, logits, pooled, d, arena = _head_fwd(x0, x1, js, labels, bundle, weight, label_smoothing)
+        loss, logits, pooled, d, arena = _head_fwd(x0, x1, js, labels, bundle, weight, label_smoothing, labels_b, lam)
         ctx.save_for_backward(x0, x1, labels, logits, pooled)
         ctx.d, ctx.keep, ctx.bundle, ctx.weight = d, arena, bundle, weight  # (the descriptor holds the weights' address)
+        ctx.mix = (labels_b, lam)  # ... and, on a mixed batch, theirs
         ctx.set_materialize_grads(False)
         return loss, logits, pooled
 
@@ -1267,11 +1293,12 @@ class _Head(torch.autograd.Function):
     def backward(ctx, g_loss, g_logits, g_pooled):
         _ensure_backward_join()
         x0, x1, labels, logits, pooled = ctx.saved_tensors
-        d, bundle = ctx.d, ctx.bundle
+        md = ctx.d if isinstance(ctx.d, _lib.HeadMixDesc) else None  # a mixed batch: d2r_head_mix_bwd on the wider descriptor
+        d, bundle = ctx.d if md is None else md.head, ctx.bundle
         d_x0, d_x1 = torch.empty_like(x0), torch.empty_like(x1)
         d_js = torch.empty((), dtype=torch.float32, device=x0.device)
         if g_loss is None and g_logits is None and g_pooled is None:
-            return d_x0.zero_(), d_x1.zero_(), d_js.zero_(), None, None, None, None, None
+            return d_x0.zero_(), d_x1.zero_(), d_js.zero_(), None, None, None, None, None, None, None
         # gradients arriving at the logits / Block's output (a second loss on them) are added to the cross-entropy path inside the call
         g_loss = torch.zeros((), dtype=torch.float32, device=x0.device) if g_loss is None else g_loss.contiguous().float()
         g_logits = None if g_logits is None else g_logits.contiguous().float()
@@ -1283,26 +1310,32 @@ class _Head(torch.autograd.Function):
         d.splitk_ws, d.splitk_bytes = ws.data_ptr(), ws.numel()
         d.d_loss, d.d_x0, d.d_x1, d.d_js = g_loss.data_ptr(), d_x0.data_ptr(), d_x1.data_ptr(), d_js.data_ptr()
         d.scratch, d.scratch_bytes = scratch.data_ptr(), scratch.numel()
-        _lib.call("d2r_head_bwd", C.byref(d), _stream(), meta=dict(group="head_bwd"))
+        if md is None:
+            _lib.call("d2r_head_bwd", C.byref(d), _stream(), meta=dict(group="head_bwd"))
+        else:
+            _lib.call("d2r_head_mix_bwd", C.byref(md), _stream(), meta=dict(group="head_bwd"))
         ctx.keep = None
         for p in bundle.params:  # data-parallel bucket readiness: every sink of the head is written now
             cb = getattr(p, "_d2r_ready_cb", None)
             if cb is not None:
                 cb(p)
-        return d_x0, d_x1, d_js, None, None, None, None, None
+        return d_x0, d_x1, d_js, None, None, None, None, None, None, None
 
 
-def head(x0, x1, js, labels, bundle: HeadBundle, weight=None, label_smoothing=0.0):
+def head(x0, x1, js, labels, bundle: HeadBundle, weight=None, label_smoothing=0.0, labels_b=None, lam=None):
     """Block fusion + fc + cross entropy + (ce + js) as a single autograd node: -> (loss, logits [B, classes], pooled [B, 768]).
     labels=None: prediction, -> (None, logits, pooled) from the same launches minus the loss; only outside autograd recording.
-    weight (fp32 [classes] on the device) / label_smoothing: the options of torch's CrossEntropyLoss, inside the same call."""
+    weight (fp32 [classes] on the device) / label_smoothing: the options of torch's CrossEntropyLoss, inside the same call.
+    labels_b (integer [B]) / lam (fp32 [B] on the device), both or neither: the mixed-label cross entropy of a MixUp / CutMix batch
+    (d2r_head_mix_fwd / d2r_head_mix_bwd); without them the call is what it was."""
     weight, label_smoothing = _loss_options(weight, label_smoothing, bundle.classes, x0.device, "head")
+    labels_b, lam = _mix_options(labels, labels_b, lam, "head")
     if labels is None:
         if torch.is_grad_enabled() and any(t.requires_grad for t in (x0, x1, *bundle.params)):
             raise _lib.D2RError("head: a label-free call has no loss to differentiate; call it under torch.no_grad()")
         _, logits, pooled, _, _ = _head_fwd(x0.contiguous(), x1.contiguous(), None, None, bundle)
         return None, logits, pooled
-    return _Head.apply(x0, x1, js, labels, bundle.params[0], bundle, weight, label_smoothing)
+    return _Head.apply(x0, x1, js, labels, bundle.params[0], bundle, weight, label_smoothing, labels_b, lam)
 
 
 def interaction(own, other, bundle: InteractionBundle, train: bool):
@@ -1912,11 +1945,43 @@ class _CrossEntropyEx(torch.autograd.Function):
         return d, None, None, None
 
 
-def cross_entropy(logits, labels, weight=None, label_smoothing=0.0):
+class _CrossEntropyMix(torch.autograd.Function):
+    """Two labels per row (MixUp / CutMix): d2r_ce_mix_fwd / d2r_ce_mix_bwd."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, labels_b, lam, weight, eps):
+        logits = logits.contiguous()
+        labels = labels.contiguous().long()
+        B, Cn = logits.shape
+        out = torch.empty((), dtype=torch.float32, device=logits.device)
+        _lib.call("d2r_ce_mix_fwd", logits.data_ptr(), labels.data_ptr(), labels_b.data_ptr(), lam.data_ptr(), _ptr(weight), eps, B, Cn,
+                  out.data_ptr(), _stream())
+        ctx.save_for_backward(logits, labels, labels_b, lam)
+        ctx.weight, ctx.eps = weight, eps
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        _ensure_backward_join()
+        logits, labels, labels_b, lam = ctx.saved_tensors
+        g = g.contiguous()
+        B, Cn = logits.shape
+        d = torch.empty_like(logits)
+        _lib.call("d2r_ce_mix_bwd", logits.data_ptr(), labels.data_ptr(), labels_b.data_ptr(), lam.data_ptr(), _ptr(ctx.weight), ctx.eps,
+                  B, Cn, g.data_ptr(), d.data_ptr(), _stream())
+        return d, None, None, None, None, None
+
+
+def cross_entropy(logits, labels, weight=None, label_smoothing=0.0, labels_b=None, lam=None):
     """Mean cross entropy of fp32 [B, C] logits; weight (fp32 [C] on the device) and label_smoothing as in
-    torch.nn.functional.cross_entropy.  Without either option: d2r_ce_fwd / d2r_ce_bwd, as before."""
+    torch.nn.functional.cross_entropy.  Without either option: d2r_ce_fwd / d2r_ce_bwd, as before.
+    labels_b (integer [B]) / lam (fp32 [B] on the device), both or neither: the target of row b is lam[b] onehot(labels[b]) +
+    (1 - lam[b]) onehot(labels_b[b]) (MixUp / CutMix); no gradient reaches lam."""
     assert logits.dtype == torch.float32
     weight, eps = _loss_options(weight, label_smoothing, logits.shape[-1], logits.device, "cross_entropy")
+    labels_b, lam = _mix_options(labels, labels_b, lam, "cross_entropy")
+    if labels_b is not None:
+        return _CrossEntropyMix.apply(logits, labels, labels_b, lam, weight, eps)
     if weight is None and eps == 0.0:
         return _CrossEntropy.apply(logits, labels)
     return _CrossEntropyEx.apply(logits, labels, weight, eps)
@@ -2032,6 +2097,23 @@ class _ClipEmbed(torch.autograd.Function):
         gemm(GEMM_TN, E, K, B * npatch, gp.data_ptr(), E, patches.data_ptr(), K, dw.data_ptr(), K, dtype=_dt(g), c_dtype=F32,
              beta=0.0, splitk_ws=_workspace(64 << 20, g.device))
         return None, dw.view(wshape), None, dcls, dpos, None
+
+
+def image_mix(pixels: torch.Tensor, h_desc: torch.Tensor, desc: torch.Tensor) -> torch.Tensor:
+    """MixUp / CutMix of a finished pixel batch (d2r_image_mix, K24): a new fp32 [B, 3, S, S] tensor.  desc: int32 [B, 8] on the
+    pixels' device, {partner, fp32 bits of a, x0, y0, w, h, 0, 0} per sample; h_desc its host copy (checked before the launch)."""
+    _require_cuda(pixels, desc)
+    if pixels.dtype != torch.float32 or pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.shape[2] != pixels.shape[3]:
+        raise _lib.D2RError(f"image_mix: pixels must be fp32 [B, 3, S, S], got {pixels.dtype} {tuple(pixels.shape)}")
+    B, S = pixels.shape[0], pixels.shape[2]
+    for t, where in ((h_desc, "cpu"), (desc, "cuda")):
+        if t.dtype != torch.int32 or tuple(t.shape) != (B, 8) or t.device.type != where or not t.is_contiguous():
+            raise _lib.D2RError(f"image_mix: the descriptors must be contiguous int32 [{B}, 8], one on the host and one on the device")
+    pixels = pixels.contiguous()
+    out = torch.empty_like(pixels)
+    _lib.call("d2r_image_mix", pixels.data_ptr(), out.data_ptr(), B, S, h_desc.data_ptr(), desc.data_ptr(), _stream(),
+              meta=dict(group="image_mix", bytes=3.0 * pixels.numel() * 4))
+    return out
 
 
 def clip_embed(pixels, w_master, w_compute, cls, pos, patch):

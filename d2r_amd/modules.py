@@ -914,8 +914,8 @@ class UnimoModel(D2RModule):
 
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, pixel_values=None, head=None):
         """-> (pooler_output [B,768], js_loss, aux) — models/modeling_unimo.py:786-894.
-        head = (fc Linear, labels, class weights or None, label smoothing): UnimoModelF's classifier and loss are computed here,
-        together with Block, as one C call (aux["loss"], aux["logits"]) when the one-call head applies."""
+        head = (fc Linear, labels, class weights or None, label smoothing[, labels_b, mix_lam]): UnimoModelF's classifier and loss are
+        computed here, together with Block, as one C call (aux["loss"], aux["logits"]) when the one-call head applies."""
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         if token_type_ids is None:
@@ -1050,19 +1050,25 @@ class UnimoModelF(D2RModule):
             cw = self.class_weight = cw.to(device)
         return cw
 
-    def forward(self, input_ids, attention_mask, token_type_ids, labels=None, images=None):
+    def forward(self, input_ids, attention_mask, token_type_ids, labels=None, images=None, labels_b=None, mix_lam=None):
+        """labels_b (integer [B]) / mix_lam (fp32 [B] on the device), both or neither and only with labels: the batch was mixed
+        (d2r_amd.mix) and the cross entropy takes mix_lam[b] onehot(labels[b]) + (1 - mix_lam[b]) onehot(labels_b[b]) as row b's target."""
         if images is None:
             raise ValueError("images is None")
         if labels is None and torch.is_grad_enabled():
             raise RuntimeError("UnimoModelF: a call without labels has no loss to differentiate; predict under torch.no_grad()")
+        if (labels_b is None) != (mix_lam is None):
+            raise ValueError("UnimoModelF: labels_b and mix_lam go together")
+        if labels_b is not None and labels is None:
+            raise ValueError("UnimoModelF: labels_b / mix_lam were given without labels")
         cw, eps = self._class_weight_on(images.device), self.label_smoothing
-        pooled, js_loss, aux = self.model(input_ids=input_ids, attention_mask=attention_mask,
-                                          token_type_ids=token_type_ids, pixel_values=images, head=(self.fc, labels, cw, eps))
+        pooled, js_loss, aux = self.model(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids,
+                                          pixel_values=images, head=(self.fc, labels, cw, eps, labels_b, mix_lam))
         if "loss" in aux:  # Block, fc, cross entropy and the sum were one call inside the model
             loss, logits = aux.pop("loss"), aux.pop("logits")
         else:
             logits = self.fc(pooled, fp32=True)
-            loss = None if labels is None else F.lincomb([1.0, 1.0], [F.cross_entropy(logits, labels, cw, eps), js_loss])
+            loss = None if labels is None else F.lincomb([1.0, 1.0], [F.cross_entropy(logits, labels, cw, eps, labels_b, mix_lam), js_loss])
         aux["js_loss"] = js_loss
         self.last_aux = aux
         return loss, logits

@@ -22,6 +22,9 @@ that augmentation (colour jitter in this fixed order, random grayscale, random e
 --aug_token_delete P / --aug_token_mask P / --aug_token_replace P / --aug_whole_word: per token of a training text, delete it, put
 [MASK] in its place or replace it by a random id, per piece or per whole word, in the one launch that builds the batch's token
 tensors on the device (d2r_token_augment, d2r_amd.text_augment); real and synthetic data.
+--aug_mixup A / --aug_cutmix A / --aug_mix_prob P: MixUp / CutMix of the finished training pixel batch in one launch, with a cross
+entropy against two labels per sample (d2r_image_mix, d2r_ce_mix_*, d2r_amd.mix); only the image is mixed; real and
+synthetic data.
 """
 from __future__ import annotations
 
@@ -114,6 +117,20 @@ def _aug_token(text):
     v = float(text)
     if not 0 <= v <= 1:
         raise argparse.ArgumentTypeError(f"must be in [0, 1] (0 = off), got {text}")
+    return v
+
+
+def _aug_mix_alpha(text):
+    v = float(text)
+    if not (v >= 0 and math.isfinite(v)):
+        raise argparse.ArgumentTypeError(f"must be finite and >= 0 (0 = off), got {text}")
+    return v
+
+
+def _aug_mix_prob(text):
+    v = float(text)
+    if not 0 <= v <= 1:
+        raise argparse.ArgumentTypeError(f"must be in [0, 1], got {text}")
     return v
 
 
@@ -315,6 +332,16 @@ def build_parser():
                        "behaviour; dev and test texts are never augmented; real and synthetic data")
     p.add_argument("--aug_whole_word", action="store_true", help="with --data_path: a word and its ## pieces share one --aug_token_* "
                    "decision, drawn at the word's first piece")
+    p.add_argument("--aug_mixup", default=0.0, type=_aug_mix_alpha, help="MixUp of the training images on the device: each image is "
+                   "blended with another image of its batch, lam * own + (1 - lam) * partner with lam ~ Beta(A, A) per sample, and the "
+                   "loss is taken against both labels in these shares (d2r_image_mix, d2r_ce_mix_*); only the image is mixed, the text "
+                   "stays the sample's own; finite and >= 0, 0 = off, the reference's behaviour; real and synthetic data")
+    p.add_argument("--aug_cutmix", default=0.0, type=_aug_mix_alpha, help="CutMix of the training images on the device: a box of "
+                   "1 - lam ~ Beta(A, A) of another image of the batch is pasted over each image, the label share corrected to the "
+                   "clipped box (timm's rand_bbox); with --aug_mixup too, each sample takes CutMix with probability 0.5; same rules "
+                   "as --aug_mixup")
+    p.add_argument("--aug_mix_prob", default=None, type=_aug_mix_prob, help="probability that a training sample is mixed at all, in "
+                   "[0, 1] (default 1); needs --aug_mixup or --aug_cutmix")
     p.add_argument("--pretrained", action="store_true", help="model configs, weights and image preprocessing from the local "
                    "--bert_name / --vit_name checkpoints (BertModel, CLIPModel.vision_model, preprocessor_config.json)")
     return p
@@ -369,6 +396,9 @@ def main(argv=None):
     if args.aug_whole_word and args.data_path is None:
         raise SystemExit("--aug_whole_word reads the word pieces from the vocabulary of --bert_name: synthetic ids are plain integers "
                          "without one; run without it")
+    mixing = args.aug_mixup > 0.0 or args.aug_cutmix > 0.0
+    if args.aug_mix_prob is not None and not mixing:
+        raise SystemExit("--aug_mix_prob is the probability of --aug_mixup / --aug_cutmix: give one of them too")
     try:
         class_weights = parse_class_weights(args.class_weights, args.num_classes)
     except ValueError as e:
@@ -466,6 +496,14 @@ def main(argv=None):
             raise SystemExit(f"{_TOKEN_NAMES}: {e}")
     elif args.aug_whole_word:
         logger.info("--aug_whole_word has no effect without %s", _TOKEN_NAMES)
+    mixer = None
+    if mixing and args.only_test:
+        logger.info("--aug_mixup / --aug_cutmix / --aug_mix_prob are ignored with --only_test: only training batches are mixed")
+    elif mixing:
+        # a generator of its own, seeded from (--seed, rank), as the augmenters'; the trainer holds it with and without the cache
+        from .mix import Mixer
+        mixer = Mixer(int(S), args.aug_mixup, args.aug_cutmix, 1.0 if args.aug_mix_prob is None else args.aug_mix_prob, seed=args.seed,
+                      rank=rank)
     if args.cache_dataset == "device" and args.only_test:
         logger.info("--cache_dataset device is ignored with --only_test: a single pass over the test split gains nothing")
     elif args.cache_dataset == "device":
@@ -501,6 +539,8 @@ def main(argv=None):
         trainer.predict(test_dl, args.write_path)
         return
     more = {} if text_augmenter is None else {"text_augmenter": text_augmenter}
+    if mixer is not None:
+        more["mixer"] = mixer
     trainer = MSDTrainer(train_data=train_dl, dev_data=dev_dl, test_data=test_dl, model=model, args=args, logger=logger,
                          writer=None, augmenter=augmenter, **more)
     trainer.train(clip_sd, bert_sd)  # None, None without --pretrained: randomly initialised encoders

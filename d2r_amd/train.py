@@ -18,6 +18,8 @@ state-dict key names (:210-216).  Differences, all deliberate (SURVEY.md Appendi
     never augment;
   * optional text augmentation of the TRAINING batches (``text_augmenter``, d2r_amd.text_augment: token deletion, [MASK] and
     random-id replacement in one launch on the device; a CachedLoader carries its own), under the same rules;
+  * optional MixUp / CutMix of the TRAINING batches (``mixer``, d2r_amd.mix: one launch on the finished pixel batch, after every
+    other augmentation and the same for cached and uncached loaders; the loss takes two labels per sample), under the same rules;
   * evaluate() / test() count a confusion matrix on the device (d2r_confusion_add) instead of copying labels and predictions to
     the host per batch, and log per-class precision / recall / F1 / support after the four aggregates; they return the scalar
     entries as before, the whole result (with "confusion" and "per_class") stays in last_dev_result / last_test_result.
@@ -138,8 +140,9 @@ def ingest_pretrained(model, clip_model_dict, bert_model_dict):
 
 class MSDTrainer:
     def __init__(self, train_data=None, dev_data=None, test_data=None, model=None, args=None, logger=None,
-                 writer=None, augmenter=None, *, text_augmenter=None) -> None:
+                 writer=None, augmenter=None, *, text_augmenter=None, mixer=None) -> None:
         self.train_data, self.dev_data, self.test_data = train_data, dev_data, test_data
+        self.mixer = mixer  # MixUp / CutMix of the training batches (d2r_amd.mix), after every other augmentation; None: off
         self.augmenter = augmenter  # training batches of packed images only (a CachedLoader augments its own batches)
         self.text_augmenter = text_augmenter  # training batches' token tensors (a CachedLoader with its own: None here)
         self.model, self.args = model, args
@@ -242,6 +245,8 @@ class MSDTrainer:
         text_augmenter = self.text_augmenter or getattr(self.train_data, "text_augmenter", None)
         if text_augmenter is not None:
             self.logger.info("  Text augmentation of the training batches: %s", text_augmenter.describe())
+        if self.mixer is not None:
+            self.logger.info("  MixUp / CutMix of the training batches: %s", self.mixer.describe())
         run_loss = torch.zeros((), dtype=torch.float32, device=self.args.device)
         clipping = self.optimizer.max_grad_norm is not None
         grad_norm = torch.zeros((), dtype=torch.float32, pin_memory=torch.cuda.is_available()) if clipping else None
@@ -260,6 +265,9 @@ class MSDTrainer:
                 if self.step == warm + 1 and t_mark is None:
                     t_mark = time.time()
                 packed, batch = batch, self._to_device(batch, self.augmenter, self.text_augmenter)
+                if self.mixer is not None:  # after every other augmentation, cached loader or not: the images and the labels only
+                    images, labels, labels_b, lam = self.mixer.apply(batch[5], batch[4])
+                    batch = (*batch[:4], labels, images, labels_b, lam)
                 self.decode_log.note(packed)
                 self.dp.begin_step()
                 (loss, logits), labels = self._step(batch, mode="train")
@@ -449,7 +457,11 @@ class MSDTrainer:
                 "paths_image": paths_image, "metrics": metrics, "samples_per_sec": self.samples_per_sec}
 
     def _step(self, batch, mode="train"):
-        input_ids, input_mask, segment_ids, img_mask, labels, images = batch  # img_mask is unused (train.py:281-284)
-        outputs = self.model(input_ids=input_ids, attention_mask=input_mask, token_type_ids=segment_ids,
-                             labels=labels, images=images)
+        input_ids, input_mask, segment_ids, img_mask, labels, images = batch[:6]  # img_mask is unused (train.py:281-284)
+        if len(batch) == 6:
+            outputs = self.model(input_ids=input_ids, attention_mask=input_mask, token_type_ids=segment_ids,
+                                 labels=labels, images=images)
+        else:  # a mixed training batch: (..., labels_b, lam) from the mixer
+            outputs = self.model(input_ids=input_ids, attention_mask=input_mask, token_type_ids=segment_ids,
+                                 labels=labels, images=images, labels_b=batch[6], mix_lam=batch[7])
         return outputs, labels

@@ -314,6 +314,23 @@ int d2r_ce_fwd_ex(const float* logits, const int64_t* labels, const float* class
                   float label_smoothing, int B, int C, float* loss /*[1]*/, void* stream);
 int d2r_ce_bwd_ex(const float* logits, const int64_t* labels, const float* class_weight, float label_smoothing,
                   int B, int C, const float* dloss /*[1]*/, float* dlogits /*[B,C]*/, void* stream);
+/* d2r_ce_mix_fwd / d2r_ce_mix_bwd: cross entropy against TWO labels per row (MixUp / CutMix, d2r_amd/mix.py): the formula of
+ * d2r_ce_fwd_ex / d2r_ce_bwd_ex with the one-hot target replaced by lam_b onehot(y_b) + (1 - lam_b) onehot(y2_b).  With
+ * lp = log_softmax(logits), w == 1 when class_weight is NULL, y = labels[b], y2 = labels_b[b], lam = lam[b] (fp32 [B] on the device):
+ *   hard_b(c)    = (1-e) ( lam w[y] [c == y] + (1-lam) w[y2] [c == y2] )
+ *   loss         = sum_b [ sum_c hard_b(c) (-lp[b,c]) + (e/C) sum_c w[c] (-lp[b,c]) ] / W,   W = sum_b ( lam w[y] + (1-lam) w[y2] )
+ *   dlogits[b,c] = dloss / W * ( p[b,c] (sum_k hard_b(k) + (e/C) sum_k w[k]) - hard_b(c) - (e/C) w[c] )
+ * With every lam == 1 it is the formula of d2r_ce_*_ex exactly, and the result has their bits.  Without class weights it is
+ * torch.nn.functional.cross_entropy(logits, lam onehot(y) + (1-lam) onehot(y2), label_smoothing=e) - probability targets.
+ * labels_b and lam are both given or both NULL; only one of them is refused.  Both NULL forwards to d2r_ce_fwd_ex / d2r_ce_bwd_ex
+ * (which forward to d2r_ce_fwd / d2r_ce_bwd without options): bit-identical to a call without them.  label_smoothing outside
+ * [0, 1) is refused.  A lam outside [0, 1], like a label outside [0, C), is the caller's error (it lives on the device).  The same
+ * launch shapes as the _ex kernels; the backward kernel sums W again in every workgroup (no workspace, no atomics). */
+int d2r_ce_mix_fwd(const float* logits, const int64_t* labels, const int64_t* labels_b /* [B] or NULL */,
+                   const float* lam /* fp32 [B] on the device, or NULL */, const float* class_weight /* [C] or NULL */,
+                   float label_smoothing, int B, int C, float* loss /*[1]*/, void* stream);
+int d2r_ce_mix_bwd(const float* logits, const int64_t* labels, const int64_t* labels_b, const float* lam, const float* class_weight,
+                   float label_smoothing, int B, int C, const float* dloss /*[1]*/, float* dlogits /*[B,C]*/, void* stream);
 /* Predicted class per row of fp32 X[rows, cols] (row stride ld >= cols): idx[r] = argmax_c X[r, c], with torch.argmax's rules -
  * a tie goes to the lowest index, a NaN counts as the maximum and the first NaN of a row wins, +-inf compare as usual.
  * Replaces logits.argmax(-1) at modules/train.py:181,243 (prediction from a checkpoint).  rows == 0 launches nothing. */
@@ -598,6 +615,17 @@ size_t d2r_head_bwd_scratch(int B, int E, int mm, int chunks, int rank, int clas
  * differentiate without them). */
 int d2r_head_fwd(const d2r_head_desc* d, void* stream);
 int d2r_head_bwd(const d2r_head_desc* d, void* stream);
+/* The head on a MixUp / CutMix batch: d2r_head_desc with two fields after its end - the second label per row ([B]) and the first
+ * label's share (fp32 [B] on the device).  d2r_head_desc itself keeps its layout, so callers of d2r_head_fwd / d2r_head_bwd are
+ * not disturbed.  d2r_head_mix_fwd / d2r_head_mix_bwd are d2r_head_fwd / d2r_head_bwd with d2r_ce_mix_fwd / d2r_ce_mix_bwd as the cross
+ * entropy; with labels_b and mix_lam both NULL they take exactly the branches of d2r_head_fwd / d2r_head_bwd (only one of the two
+ * is refused). */
+typedef struct {
+  d2r_head_desc head;
+  const int64_t* labels_b; const float* mix_lam;
+} d2r_head_mix_desc;
+int d2r_head_mix_fwd(const d2r_head_mix_desc* d, void* stream);
+int d2r_head_mix_bwd(const d2r_head_mix_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K12 embeddings (models/modeling_unimo.py:87-118, 272-331)
@@ -726,6 +754,18 @@ int d2r_clip_cache_augment_photo(const uint8_t* cache, int64_t cache_rows, const
                                  const d2r_clip_augment_desc* h_aug, const d2r_clip_augment_desc* aug,
                                  const d2r_clip_photo_desc* h_photo, const d2r_clip_photo_desc* photo, int B, int S, const float* h_norm,
                                  float rescale, float* out, void* ws, size_t ws_bytes, void* stream);
+/* K24  MixUp / CutMix of a finished pixel batch (d2r_amd/mix.py, --aug_mixup / --aug_cutmix).  in and out are fp32 [B, 3, S, S], the
+ * pixel values every batch-building path produces; out is OVERWRITTEN and must not overlap in (sample b reads sample partner_b).
+ * One descriptor of eight int32 per sample: {partner, the fp32 bits of a, x0, y0, w, h, 0, 0}.  For sample b, channel c, pixel (y, x):
+ *   out[b,c,y,x] = in[partner,c,y,x]                               if x0 <= x < x0+w and y0 <= y < y0+h   (the box; bit for bit)
+ *                = in[b,c,y,x]                                     else if a == 1                         (a copy, bit for bit)
+ *                = fl(fl(a * in[b,c,y,x]) + fl(fl(1-a) * in[partner,c,y,x]))   otherwise, in fp32, every operation rounded on its own.
+ * w == 0 or h == 0 is an empty box.  a == 1 with an empty box still writes the copy.  One float4 per lane when S is a multiple of 4
+ * and in and out are 16-byte aligned, single loads and stores otherwise; the partner is not read where it is not needed.
+ * h_desc is the host copy of desc.  Refused before anything is enqueued (a refused call writes nothing): a null pointer, B outside
+ * [1, 65535], S outside [1, 4096], in / out / desc not 4-byte aligned, out overlapping in, a partner outside [0, B), an a that is
+ * not finite or outside [0, 1], a negative w or h, a box that does not lie inside [0, S] x [0, S]. */
+int d2r_image_mix(const float* in, float* out, int B, int S, const int32_t* h_desc, const int32_t* desc, void* stream);
 /* K23  Text augmentation on the token rows (d2r_amd/text_augment.py, --aug_token_delete / --aug_token_mask / --aug_token_replace /
  * --aug_whole_word).  d2r_token_augment builds the three token tensors of a batch from their source rows - what three d2r_gather_rows
  * calls do - and deletes, masks or replaces tokens per sample on the way.
