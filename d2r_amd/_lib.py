@@ -87,6 +87,10 @@ class HeadMixDesc(C.Structure):  # d2r_head_mix_desc: the head's descriptor, the
     _fields_ = [("head", HeadDesc), ("labels_b", vp), ("mix_lam", vp)]
 
 
+class HeadFocalDesc(C.Structure):  # d2r_head_focal_desc: the mixed head's descriptor, then the focal loss's exponent
+    _fields_ = [("mix", HeadMixDesc), ("focal_gamma", f32)]
+
+
 class ClipImageDesc(C.Structure):
     _fields_ = [("src_offset", i64)] + [(n, i32) for n in ("H", "W", "rh", "rw", "top", "left", "kx", "ky", "bx", "cx", "by", "cy",
                                                           "row0", "nrows")] + [("ws_offset", i64)]
@@ -123,6 +127,8 @@ SIGNATURES = {
     "d2r_head_bwd": (i32, [C.POINTER(HeadDesc), vp]),
     "d2r_head_mix_fwd": (i32, [C.POINTER(HeadMixDesc), vp]),
     "d2r_head_mix_bwd": (i32, [C.POINTER(HeadMixDesc), vp]),
+    "d2r_head_focal_fwd": (i32, [C.POINTER(HeadFocalDesc), vp]),
+    "d2r_head_focal_bwd": (i32, [C.POINTER(HeadFocalDesc), vp]),
     "d2r_version": (C.c_char_p, []),
     "d2r_last_error": (C.c_char_p, []),
     "d2r_gemm": (i32, [C.POINTER(GemmDesc), vp]),
@@ -204,6 +210,8 @@ SIGNATURES = {
     "d2r_ce_bwd_ex": (i32, [vp, vp, vp, f32, i32, i32, vp, vp, vp]),
     "d2r_ce_mix_fwd": (i32, [vp, vp, vp, vp, vp, f32, i32, i32, vp, vp]),
     "d2r_ce_mix_bwd": (i32, [vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp]),
+    "d2r_ce_focal_fwd": (i32, [vp, vp, vp, vp, vp, f32, f32, i32, i32, vp, vp]),
+    "d2r_ce_focal_bwd": (i32, [vp, vp, vp, vp, vp, f32, f32, i32, i32, vp, vp, vp]),
     "d2r_argmax_rows": (i32, [vp, i64, i64, i32, vp, vp]),
     "d2r_confusion_add": (i32, [vp, i64, vp, i64, i32, vp, vp]),
     "d2r_block_merge_fwd": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),

@@ -941,8 +941,9 @@ extern "C" size_t d2r_head_bwd_scratch(int B, int E, int mm, int chunks, int ran
   return Z.off;
 }
 
-// labels_b / mix_lam: the two fields of d2r_head_mix_desc (NULL from d2r_head_fwd / d2r_head_bwd)
-static int head_fwd(const d2r_head_desc* D, const int64_t* labels_b, const float* mix_lam, void* stream) {
+// labels_b / mix_lam: the two fields of d2r_head_mix_desc (NULL from d2r_head_fwd / d2r_head_bwd); focal_gamma: the field of
+// d2r_head_focal_desc (0 from the other two pairs: exactly their branches)
+static int head_fwd(const d2r_head_desc* D, const int64_t* labels_b, const float* mix_lam, float focal_gamma, void* stream) {
   HeadDims h;
   TRY(head_dims(D, h));
   D2R_REQUIRE(D->x0 && D->x1 && D->logits && D->pooled && D->arena, "d2r_head_fwd: null pointer");
@@ -960,7 +961,10 @@ static int head_fwd(const d2r_head_desc* D, const int64_t* labels_b, const float
   TRY(lin(c, h.B, h.E, h.mm, a.z, h.mm, D->lin_out, D->pooled));
   TRY(lin(c, h.B, h.classes, h.E, D->pooled, h.E, D->fc, D->logits));
   if (!D->labels) return D2R_OK;  // prediction: logits and pooled only
-  if (labels_b || mix_lam)  // MixUp / CutMix: two labels per row (one of the two alone is refused there)
+  if (focal_gamma != 0.f)  // focal loss, with or without a second label
+    TRY(d2r_ce_focal_fwd(D->logits, D->labels, labels_b, mix_lam, D->class_weight, D->label_smoothing, focal_gamma, h.B, h.classes, a.ce,
+                         stream));
+  else if (labels_b || mix_lam)  // MixUp / CutMix: two labels per row (one of the two alone is refused there)
     TRY(d2r_ce_mix_fwd(D->logits, D->labels, labels_b, mix_lam, D->class_weight, D->label_smoothing, h.B, h.classes, a.ce, stream));
   else if (D->class_weight || D->label_smoothing != 0.f)
     TRY(d2r_ce_fwd_ex(D->logits, D->labels, D->class_weight, D->label_smoothing, h.B, h.classes, a.ce, stream));
@@ -971,7 +975,7 @@ static int head_fwd(const d2r_head_desc* D, const int64_t* labels_b, const float
   return d2r_lincomb(xs, coef, 2, D->loss, stream);
 }
 
-static int head_bwd(const d2r_head_desc* D, const int64_t* labels_b, const float* mix_lam, void* stream) {
+static int head_bwd(const d2r_head_desc* D, const int64_t* labels_b, const float* mix_lam, float focal_gamma, void* stream) {
   HeadDims h;
   TRY(head_dims(D, h));
   D2R_REQUIRE(D->labels, "d2r_head_bwd: labels are required (a label-free forward has no loss to differentiate)");
@@ -987,7 +991,10 @@ static int head_bwd(const d2r_head_desc* D, const int64_t* labels_b, const float
   head_plan(A, h, a);
   head_plan_bwd(Z, h, g);
   TRY(d2r_axpby(D2R_F32, 1.f, D->d_loss, 0.f, D->d_js, 1, stream));  // loss = ce + js
-  if (labels_b || mix_lam)
+  if (focal_gamma != 0.f)
+    TRY(d2r_ce_focal_bwd(D->logits, D->labels, labels_b, mix_lam, D->class_weight, D->label_smoothing, focal_gamma, h.B, h.classes,
+                         D->d_loss, g.dlogits, stream));
+  else if (labels_b || mix_lam)
     TRY(d2r_ce_mix_bwd(D->logits, D->labels, labels_b, mix_lam, D->class_weight, D->label_smoothing, h.B, h.classes, D->d_loss,
                        g.dlogits, stream));
   else if (D->class_weight || D->label_smoothing != 0.f)
@@ -1009,14 +1016,26 @@ static int head_bwd(const d2r_head_desc* D, const int64_t* labels_b, const float
   return dwg(c, h.B, h.mm, h.E, g.dh1, h.mm, D->x1, h.E, D->lin1);
 }
 
-extern "C" int d2r_head_fwd(const d2r_head_desc* D, void* stream) { return head_fwd(D, nullptr, nullptr, stream); }
-extern "C" int d2r_head_bwd(const d2r_head_desc* D, void* stream) { return head_bwd(D, nullptr, nullptr, stream); }
+extern "C" int d2r_head_fwd(const d2r_head_desc* D, void* stream) { return head_fwd(D, nullptr, nullptr, 0.f, stream); }
+extern "C" int d2r_head_bwd(const d2r_head_desc* D, void* stream) { return head_bwd(D, nullptr, nullptr, 0.f, stream); }
 extern "C" int d2r_head_mix_fwd(const d2r_head_mix_desc* D, void* stream) {
   D2R_REQUIRE(D, "d2r_head_mix_fwd: null descriptor");
-  return head_fwd(&D->head, D->labels_b, D->mix_lam, stream);
+  return head_fwd(&D->head, D->labels_b, D->mix_lam, 0.f, stream);
 }
 extern "C" int d2r_head_mix_bwd(const d2r_head_mix_desc* D, void* stream) {
   D2R_REQUIRE(D, "d2r_head_mix_bwd: null descriptor");
-  return head_bwd(&D->head, D->labels_b, D->mix_lam, stream);
+  return head_bwd(&D->head, D->labels_b, D->mix_lam, 0.f, stream);
 }
 
+extern "C" int d2r_head_focal_fwd(const d2r_head_focal_desc* D, void* stream) {
+  D2R_REQUIRE(D, "d2r_head_focal_fwd: null descriptor");
+  D2R_REQUIRE(D->focal_gamma >= 0.f && D->focal_gamma < INFINITY, "d2r_head_focal_fwd: focal_gamma %g must be finite and >= 0",
+              (double)D->focal_gamma);
+  return head_fwd(&D->mix.head, D->mix.labels_b, D->mix.mix_lam, D->focal_gamma, stream);
+}
+extern "C" int d2r_head_focal_bwd(const d2r_head_focal_desc* D, void* stream) {
+  D2R_REQUIRE(D, "d2r_head_focal_bwd: null descriptor");
+  D2R_REQUIRE(D->focal_gamma >= 0.f && D->focal_gamma < INFINITY, "d2r_head_focal_bwd: focal_gamma %g must be finite and >= 0",
+              (double)D->focal_gamma);
+  return head_bwd(&D->mix.head, D->mix.labels_b, D->mix.mix_lam, D->focal_gamma, stream);
+}

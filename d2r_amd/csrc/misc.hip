@@ -600,6 +600,149 @@ extern "C" int d2r_ce_mix_bwd(const float* logits, const int64_t* labels, const 
   return d2r_check_launch("d2r_ce_mix_bwd");
 }
 
+// Focal cross entropy (--focal_gamma): every row's term of the kernels above, scaled by u_b^g, the g-th power of the probability
+// mass that is NOT on the row's target t_b(c) = lam_b [c == y_b] + (1 - lam_b) [c == y2_b] (the one-hot of y_b without a pair):
+//   a_b(c) = (1-e) w[c] t_b(c) + (e/C) w[c],   row_b = sum_c a_b(c) (-lp[b,c]),   q_b = sum_c t_b(c) p[b,c]
+//   u_b = sum_c (1 - t_b(c)) p[b,c] = su_b / s_b,   loss = sum_b u_b^g row_b / W,   W = sum_b sum_c t_b(c) w[c]   (as above)
+// s_b is the row's sum of exponentials and su_b the same sum with every term scaled by 1 - t_b(c): a sum of non-negative terms, never
+// 1 - q_b (which cancels when the target's probability is near 1).  1 - t_b is written out per class - 1 - lam_b at y_b and lam_b at
+// y2_b, 0 where the two labels are one class or there is no pair, 1 elsewhere - so that no rounding of lam + (1 - lam) leaks a share
+// of the target into u_b.  u_b^g = exp(g (log su_b - log s_b)); su_b == 0 (C == 1, or the other classes underflow) gives u_b^g = 0.
+// The same launch shapes and fixed-order block_sum as the kernels above; focal_gamma == 0 never reaches these kernels.
+struct FocalRow {
+  float m, s, su;       // max, sum of exponentials, the same sum over the classes off the target
+  float nt_y, nt_y2;    // 1 - t_b at y and at y2
+  float h1, h2;         // (1-e) w[y] lam, (1-e) w[y2] (1 - lam): the hard part of a_b
+  float l1, l2;         // lam, 1 - lam (1, 0 without a pair)
+  float t_y, t_y2;      // t_b at y and at y2 (1 where the two labels are one class)
+  float wt;             // sum_c t_b(c) w[c]
+  int64_t y, y2;
+};
+__device__ __forceinline__ FocalRow focal_row(const float* __restrict__ x, int C, int64_t y, bool pair, int64_t y2, float lam,
+                                              const float* __restrict__ cw, float eps) {
+  FocalRow r;
+  r.y = y, r.y2 = pair ? y2 : y;
+  r.l1 = pair ? lam : 1.f, r.l2 = pair ? 1.f - lam : 0.f;
+  const bool two = r.y2 != r.y;
+  r.t_y = two ? r.l1 : 1.f, r.t_y2 = two ? r.l2 : 1.f;
+  r.nt_y = two ? r.l2 : 0.f, r.nt_y2 = two ? r.l1 : 0.f;
+  const float wy = cw ? cw[r.y] : 1.f, wy2 = cw ? cw[r.y2] : 1.f;
+  r.h1 = (1.f - eps) * wy * r.l1, r.h2 = (1.f - eps) * wy2 * r.l2;
+  r.wt = r.l1 * wy + r.l2 * wy2;
+  r.m = -INFINITY;
+  for (int c = 0; c < C; ++c) r.m = fmaxf(r.m, x[c]);
+  r.s = 0.f, r.su = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float e = expf(x[c] - r.m);
+    r.s += e;
+    r.su += (c == r.y ? r.nt_y : c == r.y2 ? r.nt_y2 : 1.f) * e;
+  }
+  return r;
+}
+// u_b^g for g > 0
+__device__ __forceinline__ float focal_pow(const FocalRow& r, float g) { return r.su > 0.f ? expf(g * (logf(r.su) - logf(r.s))) : 0.f; }
+// row_b = sum_c a_b(c) (-lp[b,c])
+__device__ __forceinline__ float focal_row_term(const FocalRow& r, const float* __restrict__ x, int C, const float* __restrict__ cw,
+                                                float e_c) {
+  const float lse = r.m + logf(r.s);
+  float sm = 0.f;  // sum_c w[c] (-lp[b,c])
+  if (e_c != 0.f)
+    for (int c = 0; c < C; ++c) sm += (cw ? cw[c] : 1.f) * (lse - x[c]);
+  return r.h1 * (lse - x[r.y]) + r.h2 * (lse - x[r.y2]) + e_c * sm;
+}
+__global__ __launch_bounds__(256) void ce_focal_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                           const int64_t* __restrict__ labels_b, const float* __restrict__ lam,
+                                                           const float* __restrict__ cw, float eps, float gamma, int B, int C,
+                                                           float* __restrict__ loss) {
+  __shared__ float sh[16];
+  const float e_c = eps / (float)C;
+  float acc = 0.f, wacc = 0.f;
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const float* x = logits + (int64_t)b * C;
+    const FocalRow r = focal_row(x, C, labels[b], labels_b != nullptr, labels_b ? labels_b[b] : 0, lam ? lam[b] : 1.f, cw, eps);
+    const float ug = focal_pow(r, gamma);
+    if (ug > 0.f) acc += ug * focal_row_term(r, x, C, cw, e_c);
+    wacc += r.wt;
+  }
+  const float t = block_sum(acc, sh);
+  const float wsum = cw ? block_sum(wacc, sh) : (float)B;  // without class weights W is B exactly
+  if (threadIdx.x == 0) loss[0] = t / wsum;
+}
+// dlogits[b,c] = dloss / W * ( u_b^g (p[b,c] sum_k a_b(k) - a_b(c)) - g u_b^g row_b (p[b,c] t_b(c) - r_b(c) q_b) ),
+// r_b(c) = p[b,c] (1 - t_b(c)) / u_b = (1 - t_b(c)) exp(x[b,c] - m_b) / su_b in [0, 1].  Written this way nothing cancels: neither
+// p - r nor t - q is formed, and u_b^(g-1), which overflows for a small g, never is.  A row with u_b^g == 0 has gradient 0.  W is
+// summed again by every workgroup, as in ce_mix_bwd_kernel.
+__global__ __launch_bounds__(256) void ce_focal_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                           const int64_t* __restrict__ labels_b, const float* __restrict__ lam,
+                                                           const float* __restrict__ cw, float eps, float gamma, int B, int C,
+                                                           const float* __restrict__ dloss, float* __restrict__ dlogits) {
+  __shared__ float sh[16];
+  float wsum = (float)B, wall = (float)C;  // W, sum_k w[k]
+  if (cw) {
+    float wacc = 0.f;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+      const int64_t y = labels[b];
+      const float l1 = lam ? lam[b] : 1.f;
+      wacc += labels_b ? l1 * cw[y] + (1.f - l1) * cw[labels_b[b]] : cw[y];
+    }
+    wsum = block_sum(wacc, sh);
+    wall = 0.f;
+    for (int c = 0; c < C; ++c) wall += cw[c];
+  }
+  const float sc = dloss[0] / wsum;
+  const float e_c = eps / (float)C;
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
+    const float* x = logits + (int64_t)b * C;
+    float* d = dlogits + (int64_t)b * C;
+    const FocalRow r = focal_row(x, C, labels[b], labels_b != nullptr, labels_b ? labels_b[b] : 0, lam ? lam[b] : 1.f, cw, eps);
+    const float ug = focal_pow(r, gamma);
+    if (!(ug > 0.f)) {
+      for (int c = 0; c < C; ++c) d[c] = 0.f;
+      continue;
+    }
+    const float row = focal_row_term(r, x, C, cw, e_c);
+    const float inv = 1.f / r.s;
+    const float mass = r.h1 + r.h2 + e_c * wall;  // sum_k a_b(k)
+    const float q = (r.t_y * expf(x[r.y] - r.m) + (r.y2 != r.y ? r.t_y2 * expf(x[r.y2] - r.m) : 0.f)) * inv;
+    const float k2 = gamma * ug * row;
+    for (int c = 0; c < C; ++c) {
+      const float e = expf(x[c] - r.m), p = e * inv;
+      const float t = c == r.y ? r.t_y : c == r.y2 ? r.t_y2 : 0.f;
+      const float nt = c == r.y ? r.nt_y : c == r.y2 ? r.nt_y2 : 1.f;
+      const float a = (c == r.y ? r.h1 : 0.f) + (c == r.y2 ? r.h2 : 0.f) + e_c * (cw ? cw[c] : 1.f);
+      d[c] = sc * (ug * (p * mass - a) - k2 * (p * t - nt * e / r.su * q));  // (a quotient in [0, 1]; 1 / su_b can overflow)
+    }
+  }
+}
+static int ce_focal_check(const char* who, const int64_t* labels_b, const float* lam, float label_smoothing, float focal_gamma) {
+  D2R_REQUIRE(focal_gamma >= 0.f && focal_gamma < INFINITY, "%s: focal_gamma %g must be finite and >= 0", who, (double)focal_gamma);
+  D2R_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "%s: label_smoothing %g is outside [0, 1)", who, (double)label_smoothing);
+  D2R_REQUIRE(!labels_b == !lam, "%s: labels_b and lam must both be given or both be NULL", who);
+  return D2R_OK;
+}
+extern "C" int d2r_ce_focal_fwd(const float* logits, const int64_t* labels, const int64_t* labels_b, const float* lam,
+                                const float* class_weight, float label_smoothing, float focal_gamma, int B, int C, float* loss,
+                                void* stream) {
+  if (int rc = ce_focal_check("d2r_ce_focal_fwd", labels_b, lam, label_smoothing, focal_gamma)) return rc;
+  if (focal_gamma == 0.f)  // today's loss: today's kernels, bit for bit
+    return d2r_ce_mix_fwd(logits, labels, labels_b, lam, class_weight, label_smoothing, B, C, loss, stream);
+  D2R_REQUIRE(logits && labels && loss && B >= 1 && C >= 1, "d2r_ce_focal_fwd: bad arguments");
+  hipLaunchKernelGGL(ce_focal_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, labels_b, lam, class_weight,
+                     label_smoothing, focal_gamma, B, C, loss);
+  return d2r_check_launch("d2r_ce_focal_fwd");
+}
+extern "C" int d2r_ce_focal_bwd(const float* logits, const int64_t* labels, const int64_t* labels_b, const float* lam,
+                                const float* class_weight, float label_smoothing, float focal_gamma, int B, int C, const float* dloss,
+                                float* dlogits, void* stream) {
+  if (int rc = ce_focal_check("d2r_ce_focal_bwd", labels_b, lam, label_smoothing, focal_gamma)) return rc;
+  if (focal_gamma == 0.f)
+    return d2r_ce_mix_bwd(logits, labels, labels_b, lam, class_weight, label_smoothing, B, C, dloss, dlogits, stream);
+  D2R_REQUIRE(logits && labels && dloss && dlogits && B >= 1 && C >= 1, "d2r_ce_focal_bwd: bad arguments");
+  hipLaunchKernelGGL(ce_focal_bwd_kernel, dim3(d2r_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, labels, labels_b, lam,
+                     class_weight, label_smoothing, focal_gamma, B, C, dloss, dlogits);
+  return d2r_check_launch("d2r_ce_focal_bwd");
+}
+
 // =====================================================================================================
 // argmax over the last dim (logits.argmax(-1) at modules/train.py:181,243): thread per row, torch.argmax's rules
 // =====================================================================================================

@@ -1242,17 +1242,31 @@ def _mix_options(labels, labels_b, lam, what):
     return labels_b.contiguous().long(), lam.contiguous()
 
 
-def _head_fwd(x0, x1, js, labels, bundle: HeadBundle, weight=None, label_smoothing=0.0, labels_b=None, lam=None):
+def _focal_option(focal_gamma, what):
+    """float >= 0: the focal loss's exponent (0 = off), checked on the host."""
+    g = float(focal_gamma)
+    if not (g >= 0.0 and math.isfinite(g)):
+        raise _lib.D2RError(f"{what}: focal_gamma must be finite and >= 0, got {focal_gamma}")
+    return g
+
+
+def _head_fwd(x0, x1, js, labels, bundle: HeadBundle, weight=None, label_smoothing=0.0, labels_b=None, lam=None, focal_gamma=0.0):
     """One d2r_head_fwd call on contiguous fp32 inputs: -> (loss, logits, pooled, descriptor, arena).  labels=None: the label-free
     forward (labels, js and loss NULL; loss returned as None) - the same descriptor and launches up to the logits otherwise.
     weight / label_smoothing: the descriptor's class_weight / label_smoothing (the caller keeps `weight` alive).
     labels_b / lam (both or neither; kept alive by the caller): d2r_head_mix_fwd on a d2r_head_mix_desc, which is returned in the
-    descriptor's place (its `head` field is the descriptor)."""
+    descriptor's place (its `head` field is the descriptor).  focal_gamma != 0: d2r_head_focal_fwd on a d2r_head_focal_desc, returned
+    likewise (its `mix` field is the mixed descriptor, with or without a second label)."""
     B = x0.shape[0]
     lib = _lib.load()
-    md = None
-    if labels_b is not None:
+    md = fd = None
+    if focal_gamma != 0.0:
+        fd = _lib.HeadFocalDesc()
+        fd.focal_gamma = focal_gamma
+        md = fd.mix
+    elif labels_b is not None:
         md = _lib.HeadMixDesc()
+    if labels_b is not None:
         md.labels_b, md.mix_lam = labels_b.data_ptr(), lam.data_ptr()
     d = _lib.HeadDesc() if md is None else md.head
     d.B, d.E, d.mm, d.chunks, d.rank, d.classes = B, bundle.E, bundle.mm, bundle.chunks, bundle.rank, bundle.classes
@@ -1267,11 +1281,13 @@ def _head_fwd(x0, x1, js, labels, bundle: HeadBundle, weight=None, label_smoothi
     d.loss, d.logits, d.pooled = _ptr(loss), logits.data_ptr(), pooled.data_ptr()
     d.arena, d.arena_bytes, d.splitk_ws, d.splitk_bytes = arena.data_ptr(), arena.numel(), ws.data_ptr(), ws.numel()
     d.class_weight, d.label_smoothing = _ptr(weight), label_smoothing
-    if md is None:
+    if fd is not None:
+        _lib.call("d2r_head_focal_fwd", C.byref(fd), _stream(), meta=dict(group="head_fwd"))
+    elif md is None:
         _lib.call("d2r_head_fwd", C.byref(d), _stream(), meta=dict(group="head_fwd"))
     else:
         _lib.call("d2r_head_mix_fwd", C.byref(md), _stream(), meta=dict(group="head_fwd"))
-    return loss, logits, pooled, d if md is None else md, arena
+    return loss, logits, pooled, fd if fd is not None else d if md is None else md, arena
 
 
 class _Head(torch.autograd.Function):
@@ -1279,10 +1295,10 @@ class _Head(torch.autograd.Function):
     gradient (the end of the training graph); a gradient arriving at logits / pooled is refused."""
 
     @staticmethod
-    def forward(ctx, x0, x1, js, labels, anchor, bundle, weight, label_smoothing, labels_b=None, lam=None):
+    def forward(ctx, x0, x1, js, labels, anchor, bundle, weight, label_smoothing, labels_b=None, lam=None, focal_gamma=0.0):
         x0, x1, js = x0.contiguous(), x1.contiguous(), js.contiguous()
         labels = labels.contiguous().long()
-        loss, logits, pooled, d, arena = _head_fwd(x0, x1, js, labels, bundle, weight, label_smoothing, labels_b, lam)
+        loss, logits, pooled, d, arena = _head_fwd(x0, x1, js, labels, bundle, weight, label_smoothing, labels_b, lam, focal_gamma)
         ctx.save_for_backward(x0, x1, labels, logits, pooled)
         ctx.d, ctx.keep, ctx.bundle, ctx.weight = d, arena, bundle, weight  # (the descriptor holds the weights' address)
         ctx.mix = (labels_b, lam)  # ... and, on a mixed batch, theirs
@@ -1293,12 +1309,13 @@ class _Head(torch.autograd.Function):
     def backward(ctx, g_loss, g_logits, g_pooled):
         _ensure_backward_join()
         x0, x1, labels, logits, pooled = ctx.saved_tensors
-        md = ctx.d if isinstance(ctx.d, _lib.HeadMixDesc) else None  # a mixed batch: d2r_head_mix_bwd on the wider descriptor
+        fd = ctx.d if isinstance(ctx.d, _lib.HeadFocalDesc) else None  # the focal loss: d2r_head_focal_bwd on the widest descriptor
+        md = fd.mix if fd is not None else ctx.d if isinstance(ctx.d, _lib.HeadMixDesc) else None  # a mixed batch: d2r_head_mix_bwd
         d, bundle = ctx.d if md is None else md.head, ctx.bundle
         d_x0, d_x1 = torch.empty_like(x0), torch.empty_like(x1)
         d_js = torch.empty((), dtype=torch.float32, device=x0.device)
         if g_loss is None and g_logits is None and g_pooled is None:
-            return d_x0.zero_(), d_x1.zero_(), d_js.zero_(), None, None, None, None, None, None, None
+            return d_x0.zero_(), d_x1.zero_(), d_js.zero_(), None, None, None, None, None, None, None, None
         # gradients arriving at the logits / Block's output (a second loss on them) are added to the cross-entropy path inside the call
         g_loss = torch.zeros((), dtype=torch.float32, device=x0.device) if g_loss is None else g_loss.contiguous().float()
         g_logits = None if g_logits is None else g_logits.contiguous().float()
@@ -1310,7 +1327,9 @@ class _Head(torch.autograd.Function):
         d.splitk_ws, d.splitk_bytes = ws.data_ptr(), ws.numel()
         d.d_loss, d.d_x0, d.d_x1, d.d_js = g_loss.data_ptr(), d_x0.data_ptr(), d_x1.data_ptr(), d_js.data_ptr()
         d.scratch, d.scratch_bytes = scratch.data_ptr(), scratch.numel()
-        if md is None:
+        if fd is not None:
+            _lib.call("d2r_head_focal_bwd", C.byref(fd), _stream(), meta=dict(group="head_bwd"))
+        elif md is None:
             _lib.call("d2r_head_bwd", C.byref(d), _stream(), meta=dict(group="head_bwd"))
         else:
             _lib.call("d2r_head_mix_bwd", C.byref(md), _stream(), meta=dict(group="head_bwd"))
@@ -1319,23 +1338,25 @@ class _Head(torch.autograd.Function):
             cb = getattr(p, "_d2r_ready_cb", None)
             if cb is not None:
                 cb(p)
-        return d_x0, d_x1, d_js, None, None, None, None, None, None, None
+        return d_x0, d_x1, d_js, None, None, None, None, None, None, None, None
 
 
-def head(x0, x1, js, labels, bundle: HeadBundle, weight=None, label_smoothing=0.0, labels_b=None, lam=None):
+def head(x0, x1, js, labels, bundle: HeadBundle, weight=None, label_smoothing=0.0, labels_b=None, lam=None, focal_gamma=0.0):
     """Block fusion + fc + cross entropy + (ce + js) as a single autograd node: -> (loss, logits [B, classes], pooled [B, 768]).
     labels=None: prediction, -> (None, logits, pooled) from the same launches minus the loss; only outside autograd recording.
     weight (fp32 [classes] on the device) / label_smoothing: the options of torch's CrossEntropyLoss, inside the same call.
     labels_b (integer [B]) / lam (fp32 [B] on the device), both or neither: the mixed-label cross entropy of a MixUp / CutMix batch
-    (d2r_head_mix_fwd / d2r_head_mix_bwd); without them the call is what it was."""
+    (d2r_head_mix_fwd / d2r_head_mix_bwd); without them the call is what it was.
+    focal_gamma (finite, >= 0): the focal loss's exponent (d2r_head_focal_fwd / d2r_head_focal_bwd); 0: the calls made without it."""
     weight, label_smoothing = _loss_options(weight, label_smoothing, bundle.classes, x0.device, "head")
     labels_b, lam = _mix_options(labels, labels_b, lam, "head")
+    focal_gamma = _focal_option(focal_gamma, "head")
     if labels is None:
         if torch.is_grad_enabled() and any(t.requires_grad for t in (x0, x1, *bundle.params)):
             raise _lib.D2RError("head: a label-free call has no loss to differentiate; call it under torch.no_grad()")
         _, logits, pooled, _, _ = _head_fwd(x0.contiguous(), x1.contiguous(), None, None, bundle)
         return None, logits, pooled
-    return _Head.apply(x0, x1, js, labels, bundle.params[0], bundle, weight, label_smoothing, labels_b, lam)
+    return _Head.apply(x0, x1, js, labels, bundle.params[0], bundle, weight, label_smoothing, labels_b, lam, focal_gamma)
 
 
 def interaction(own, other, bundle: InteractionBundle, train: bool):
@@ -1972,14 +1993,47 @@ class _CrossEntropyMix(torch.autograd.Function):
         return d, None, None, None, None, None
 
 
-def cross_entropy(logits, labels, weight=None, label_smoothing=0.0, labels_b=None, lam=None):
+class _CrossEntropyFocal(torch.autograd.Function):
+    """Focal loss (focal_gamma > 0), with or without a second label per row: d2r_ce_focal_fwd / d2r_ce_focal_bwd."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, labels_b, lam, weight, eps, gamma):
+        logits = logits.contiguous()
+        labels = labels.contiguous().long()
+        B, Cn = logits.shape
+        out = torch.empty((), dtype=torch.float32, device=logits.device)
+        _lib.call("d2r_ce_focal_fwd", logits.data_ptr(), labels.data_ptr(), _ptr(labels_b), _ptr(lam), _ptr(weight), eps, gamma, B, Cn,
+                  out.data_ptr(), _stream())
+        ctx.save_for_backward(logits, labels)
+        ctx.weight, ctx.eps, ctx.gamma, ctx.mix = weight, eps, gamma, (labels_b, lam)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        _ensure_backward_join()
+        logits, labels = ctx.saved_tensors
+        labels_b, lam = ctx.mix
+        g = g.contiguous()
+        B, Cn = logits.shape
+        d = torch.empty_like(logits)
+        _lib.call("d2r_ce_focal_bwd", logits.data_ptr(), labels.data_ptr(), _ptr(labels_b), _ptr(lam), _ptr(ctx.weight), ctx.eps, ctx.gamma,
+                  B, Cn, g.data_ptr(), d.data_ptr(), _stream())
+        return d, None, None, None, None, None, None
+
+
+def cross_entropy(logits, labels, weight=None, label_smoothing=0.0, labels_b=None, lam=None, focal_gamma=0.0):
     """Mean cross entropy of fp32 [B, C] logits; weight (fp32 [C] on the device) and label_smoothing as in
     torch.nn.functional.cross_entropy.  Without either option: d2r_ce_fwd / d2r_ce_bwd, as before.
     labels_b (integer [B]) / lam (fp32 [B] on the device), both or neither: the target of row b is lam[b] onehot(labels[b]) +
-    (1 - lam[b]) onehot(labels_b[b]) (MixUp / CutMix); no gradient reaches lam."""
+    (1 - lam[b]) onehot(labels_b[b]) (MixUp / CutMix); no gradient reaches lam.
+    focal_gamma (finite, >= 0): every row's term is scaled by (1 - the probability mass on its target) ** focal_gamma, the focal loss
+    of Lin et al. (d2r_ce_focal_fwd / d2r_ce_focal_bwd, include/d2r_hip.h); 0: the calls made without it."""
     assert logits.dtype == torch.float32
     weight, eps = _loss_options(weight, label_smoothing, logits.shape[-1], logits.device, "cross_entropy")
     labels_b, lam = _mix_options(labels, labels_b, lam, "cross_entropy")
+    gamma = _focal_option(focal_gamma, "cross_entropy")
+    if gamma != 0.0:
+        return _CrossEntropyFocal.apply(logits, labels, labels_b, lam, weight, eps, gamma)
     if labels_b is not None:
         return _CrossEntropyMix.apply(logits, labels, labels_b, lam, weight, eps)
     if weight is None and eps == 0.0:

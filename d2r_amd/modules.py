@@ -914,7 +914,7 @@ class UnimoModel(D2RModule):
 
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, pixel_values=None, head=None):
         """-> (pooler_output [B,768], js_loss, aux) — models/modeling_unimo.py:786-894.
-        head = (fc Linear, labels, class weights or None, label smoothing[, labels_b, mix_lam]): UnimoModelF's classifier and loss are
+        head = (fc Linear, labels, class weights or None, label smoothing[, labels_b, mix_lam[, focal gamma]]): UnimoModelF's classifier and loss are
         computed here, together with Block, as one C call (aux["loss"], aux["logits"]) when the one-call head applies."""
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
@@ -1035,6 +1035,10 @@ class UnimoModelF(D2RModule):
         self.label_smoothing = float(getattr(args, "label_smoothing", 0.0) or 0.0)
         if not 0.0 <= self.label_smoothing < 1.0:
             raise ValueError(f"label_smoothing must be in [0, 1), got {self.label_smoothing}")
+        # The focal loss's exponent (--focal_gamma; 0 = off): on the one-call and the composite path, in train and eval mode alike.
+        self.focal_gamma = float(getattr(args, "focal_gamma", 0.0) or 0.0)
+        if not (self.focal_gamma >= 0.0 and math.isfinite(self.focal_gamma)):
+            raise ValueError(f"focal_gamma must be finite and >= 0, got {self.focal_gamma}")
         cw = getattr(args, "class_weights", None)
         self.class_weight = None
         if cw is not None:
@@ -1061,14 +1065,15 @@ class UnimoModelF(D2RModule):
             raise ValueError("UnimoModelF: labels_b and mix_lam go together")
         if labels_b is not None and labels is None:
             raise ValueError("UnimoModelF: labels_b / mix_lam were given without labels")
-        cw, eps = self._class_weight_on(images.device), self.label_smoothing
+        cw, eps, gamma = self._class_weight_on(images.device), self.label_smoothing, self.focal_gamma
         pooled, js_loss, aux = self.model(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids,
-                                          pixel_values=images, head=(self.fc, labels, cw, eps, labels_b, mix_lam))
+                                          pixel_values=images, head=(self.fc, labels, cw, eps, labels_b, mix_lam, gamma))
         if "loss" in aux:  # Block, fc, cross entropy and the sum were one call inside the model
             loss, logits = aux.pop("loss"), aux.pop("logits")
         else:
             logits = self.fc(pooled, fp32=True)
-            loss = None if labels is None else F.lincomb([1.0, 1.0], [F.cross_entropy(logits, labels, cw, eps, labels_b, mix_lam), js_loss])
+            loss = None if labels is None else F.lincomb([1.0, 1.0],
+                                                         [F.cross_entropy(logits, labels, cw, eps, labels_b, mix_lam, gamma), js_loss])
         aux["js_loss"] = js_loss
         self.last_aux = aux
         return loss, logits

@@ -14,6 +14,8 @@ allowed), --write_path writes the per-sample predictions as JSON Lines (MSDTrain
 --cache_dataset device (with --data_path) decodes every split once and serves all later batches from device memory (d2r_amd.cache).
 --ema_decay D averages the weights inside the AdamW launch; the dev / test passes and best_model.pth use the average.
 --label_smoothing E / --class_weights {none | balanced | W0,W1,...} are the options of the cross entropy (inside its kernels).
+--focal_gamma G scales every sample's cross-entropy term by (1 - the probability of its target) ** G: the focal loss, inside the same
+kernels' slot (d2r_ce_focal_*); it composes with the two options above, with MixUp / CutMix and with --dp_exact.
 --aug_crop_scale LO / --aug_flip P (with --data_path) augment the training images on the device (d2r_amd.augment).
 --aug_brightness B / --aug_contrast C / --aug_saturation S / --aug_hue H / --aug_grayscale P / --aug_erase P: the photometric half of
 that augmentation (colour jitter in this fixed order, random grayscale, random erasing), in the same launch slot.
@@ -82,6 +84,13 @@ def _label_smoothing(text):
     v = float(text)
     if not 0 <= v < 1:
         raise argparse.ArgumentTypeError(f"must be in [0, 1) (0 = off), got {text}")
+    return v
+
+
+def _focal_gamma(text):
+    v = float(text)
+    if not (v >= 0 and math.isfinite(v)):
+        raise argparse.ArgumentTypeError(f"must be finite and >= 0 (0 = off), got {text}")
     return v
 
 
@@ -289,6 +298,10 @@ def build_parser():
     p.add_argument("--class_weights", default="none", type=str, help="per-class weights of the cross entropy, as "
                    "torch.nn.CrossEntropyLoss(weight=): none (the reference's behaviour), balanced (N / (C * n_c) over the whole "
                    "training split) or --num_classes comma-separated numbers W0,W1,...; not with --dp_exact")
+    p.add_argument("--focal_gamma", default=0.0, type=_focal_gamma, help="focal loss (Lin et al. 2017): every sample's cross-entropy "
+                   "term is scaled by (1 - the probability of its target) ** G inside the loss kernels, so easy samples count less; "
+                   "finite and >= 0, 0 = off (the reference's behaviour); training, dev and test loss alike; composes with "
+                   "--class_weights (the weights act as alpha), --label_smoothing, --aug_mixup / --aug_cutmix and --dp_exact")
     p.add_argument("--dp_overlap", action="store_true")
     p.add_argument("--dp_grad_comm", default="f32", choices=["f32", "bf16"], help="dtype of the gradient buckets on the links")
     p.add_argument("--dp_shard_optimizer", action="store_true",
@@ -529,9 +542,9 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit(str(e))
     args.class_weights = class_weights  # what the model reads: a list of num_classes floats, or None
-    if class_weights is not None or args.label_smoothing:
-        logger.info("cross entropy: class weights %s, label smoothing %g%s", class_weights, args.label_smoothing,
-                    " (no loss is computed with --only_test: no effect)" if args.only_test else "")
+    if class_weights is not None or args.label_smoothing or args.focal_gamma:
+        logger.info("cross entropy: class weights %s, label smoothing %g, focal gamma %g%s", class_weights, args.label_smoothing,
+                    args.focal_gamma, " (no loss is computed with --only_test: no effect)" if args.only_test else "")
     model = UnimoModelF(args=args, vision_config=vision_config, text_config=text_config, num_classes=args.num_classes)
     if args.only_test:
         trainer = MSDTrainer(test_data=test_dl, model=model, args=args, logger=logger, writer=None)

@@ -331,6 +331,32 @@ int d2r_ce_mix_fwd(const float* logits, const int64_t* labels, const int64_t* la
                    float label_smoothing, int B, int C, float* loss /*[1]*/, void* stream);
 int d2r_ce_mix_bwd(const float* logits, const int64_t* labels, const int64_t* labels_b, const float* lam, const float* class_weight,
                    float label_smoothing, int B, int C, const float* dloss /*[1]*/, float* dlogits /*[B,C]*/, void* stream);
+/* d2r_ce_focal_fwd / d2r_ce_focal_bwd: focal loss (Lin et al. 2017; --focal_gamma) on top of d2r_ce_mix_fwd / d2r_ce_mix_bwd: every
+ * row's term is scaled by the g-th power of the probability mass that is NOT on its target, g = focal_gamma >= 0.  In the notation
+ * above, with p = exp(lp) and t_b(c) = lam_b [c == y_b] + (1 - lam_b) [c == y2_b] row b's target (the one-hot of y_b without a pair):
+ *   a_b(c) = (1-e) w[c] t_b(c) + (e/C) w[c]          (the coefficients of d2r_ce_mix_*)
+ *   row_b  = sum_c a_b(c) (-lp[b,c])                 (their per-row term)
+ *   q_b    = sum_c t_b(c) p[b,c]                     (probability mass on the target)
+ *   u_b    = 1 - q_b = sum_c (1 - t_b(c)) p[b,c]     (a sum of non-negative terms)
+ *   loss   = sum_b u_b^g row_b / W,    W = sum_b sum_c t_b(c) w[c]     (W unchanged: the normaliser of d2r_ce_mix_*)
+ *   dlogits[b,c] = dloss / W * ( u_b^g (p[b,c] sum_k a_b(k) - a_b(c))  -  g u_b^g row_b (p[b,c] t_b(c) - r_b(c) q_b) )
+ *   r_b(c) = p[b,c] (1 - t_b(c)) / u_b   in [0, 1];   u_b == 0 (C == 1, or underflow): u_b^g = 0 and r_b(c) = 0 for g > 0
+ * Without weights, smoothing or a second label it is -(1 - p_t)^g log p_t, mean over the batch; with class weights, they play the
+ * role of alpha.  The gradient is computed as written: the forms p - p (1 - t) / u and t - q cancel in fp32.  u_b is summed from
+ * its non-negative terms (never 1 - q_b), u_b^g = exp(g (log su_b - log s_b)) with s_b / su_b the row's sums of exponentials with /
+ * without the target's share, and u_b^(g-1), which overflows for a small g, is never formed.  Every output is finite for finite
+ * logits, the rows whose target leads by more than fp32's exponent range included (they contribute 0).
+ * focal_gamma == 0 forwards to d2r_ce_mix_fwd / d2r_ce_mix_bwd (which forward on to the _ex and the plain kernels): today's loss with
+ * today's bits.  labels_b and lam are both given or both NULL; only one of them is refused.  A focal_gamma that is negative, NaN or
+ * infinite and a label_smoothing outside [0, 1) are refused before anything is launched or written.  The same launch shapes as the
+ * kernels above: one workgroup of 256 threads forward, cdiv(B, 256) workgroups backward, each of which sums W again in a fixed
+ * order (no workspace, no atomics). */
+int d2r_ce_focal_fwd(const float* logits, const int64_t* labels, const int64_t* labels_b /* [B] or NULL */,
+                     const float* lam /* fp32 [B] on the device, or NULL */, const float* class_weight /* [C] or NULL */,
+                     float label_smoothing, float focal_gamma, int B, int C, float* loss /*[1]*/, void* stream);
+int d2r_ce_focal_bwd(const float* logits, const int64_t* labels, const int64_t* labels_b, const float* lam, const float* class_weight,
+                     float label_smoothing, float focal_gamma, int B, int C, const float* dloss /*[1]*/, float* dlogits /*[B,C]*/,
+                     void* stream);
 /* Predicted class per row of fp32 X[rows, cols] (row stride ld >= cols): idx[r] = argmax_c X[r, c], with torch.argmax's rules -
  * a tie goes to the lowest index, a NaN counts as the maximum and the first NaN of a row wins, +-inf compare as usual.
  * Replaces logits.argmax(-1) at modules/train.py:181,243 (prediction from a checkpoint).  rows == 0 launches nothing. */
@@ -626,6 +652,16 @@ typedef struct {
 } d2r_head_mix_desc;
 int d2r_head_mix_fwd(const d2r_head_mix_desc* d, void* stream);
 int d2r_head_mix_bwd(const d2r_head_mix_desc* d, void* stream);
+/* The head with the focal cross entropy: d2r_head_mix_desc followed by focal_gamma; the two descriptors above keep their layouts.
+ * d2r_head_focal_fwd / d2r_head_focal_bwd are d2r_head_mix_fwd / d2r_head_mix_bwd with d2r_ce_focal_fwd / d2r_ce_focal_bwd as the cross
+ * entropy (labels_b and mix_lam may both be NULL); with focal_gamma == 0 they take exactly the branches of d2r_head_mix_fwd /
+ * d2r_head_mix_bwd.  A focal_gamma that is negative, NaN or infinite is refused before anything is launched. */
+typedef struct {
+  d2r_head_mix_desc mix;
+  float focal_gamma;
+} d2r_head_focal_desc;
+int d2r_head_focal_fwd(const d2r_head_focal_desc* d, void* stream);
+int d2r_head_focal_bwd(const d2r_head_focal_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K12 embeddings (models/modeling_unimo.py:87-118, 272-331)
