@@ -236,6 +236,9 @@ SIGNATURES = {
                               vp, i64, vp, vp, vp, sz, vp]),
     "d2r_clip_embed_finish": (i32, [i32, vp, vp, vp, i32, i32, i32, vp]),
     "d2r_clip_embed_bwd": (i32, [i32, vp, i32, i32, i32, vp, vp, vp]),
+    "d2r_patchify_keep": (i32, [i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
+    "d2r_clip_embed_finish_keep": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "d2r_clip_embed_bwd_keep": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "d2r_adamw_step": (i32, [vp, vp, vp, vp, vp, i32, i64, f32, f32, f32, f32, f32, i64, f32, vp, vp]),
     "d2r_adamw_step_dev": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, f32, f32, f32, f32, vp, vp]),
     "d2r_grad_nonfinite": (i32, [vp, i64, vp, vp]),

@@ -45,7 +45,7 @@ def default_args(**over):
         lr=3e-5, warmup_ratio=0.01, eval_begin_epoch=1, seed=2023, load_path=None, save_path="./output/",
         max_seq=128, alpha=0.0, margin=0.1, DR_step=3, weight_js_1=0.1, weight_js_2=0.1, embed_size=768,
         num_head_IMRC=16, hid_IMRC=768, hid_router=768, compute_dtype=torch.float32, cleanup_output=False,
-        dp_overlap=False, drop_path=0.0)
+        dp_overlap=False, drop_path=0.0, patch_dropout=0.0)
     for k, v in over.items():
         setattr(a, k, v)
     return a

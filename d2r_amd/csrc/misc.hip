@@ -1114,3 +1114,203 @@ extern "C" int d2r_clip_embed_bwd(int dtype, const void* dX, int B, int ntok, in
   hipLaunchKernelGGL(copy_row_kernel, dim3(d2r_cdiv(D, 256)), dim3(256), 0, st, (const float*)dpos, dcls, D);  // dcls = dpos[0]
   return d2r_check_launch("d2r_clip_embed_bwd");
 }
+
+// ---- K25 PatchDropout: the three kernels above on a kept subset of the patches ----------------------------------------------------
+// keep [B, K] int32: per sample the kept patch positions, strictly increasing, each in [0, np).  The host copy is checked before any
+// launch; the kernels clamp what they read from the device copy all the same, so a device copy that differs from the host copy
+// cannot make them read outside the pixels or the position table (they never index a store by it).
+static int check_keep(const char* who, const int32_t* h_keep, const int32_t* keep, int B, int K, int np) {
+  if (!h_keep || !keep) return d2r_fail(D2R_ERR_INVALID, "%s: null keep pointer", who);
+  if (B < 1 || np < 1 || K < 1 || K > np) return d2r_fail(D2R_ERR_INVALID, "%s: need B >= 1 and 1 <= K <= np, got B %d, K %d, np %d", who, B, K, np);
+  if ((reinterpret_cast<uintptr_t>(keep) & 3u) != 0) return d2r_fail(D2R_ERR_INVALID, "%s: keep must be 4-byte aligned", who);
+  for (int b = 0; b < B; ++b) {
+    const int32_t* row = h_keep + (int64_t)b * K;
+    for (int j = 0; j < K; ++j) {
+      if (row[j] < 0 || row[j] >= np) return d2r_fail(D2R_ERR_INVALID, "%s: keep[%d][%d] = %d outside [0, %d)", who, b, j, (int)row[j], np);
+      if (j > 0 && row[j] <= row[j - 1])
+        return d2r_fail(D2R_ERR_INVALID, "%s: keep[%d] is not strictly increasing at %d (%d after %d)", who, b, j, (int)row[j], (int)row[j - 1]);
+    }
+  }
+  return D2R_OK;
+}
+__device__ __forceinline__ int keep_at(const int32_t* __restrict__ keep, int64_t i, int np) {
+  return (int)min((uint32_t)keep[i], (uint32_t)(np - 1));
+}
+
+// patches[b*K+j, (c*p+i)*p+jj] = pixels[b, c, py*p+i, px*p+jj], (py, px) the grid position of keep[b, j].
+// V == 1: one element per lane.  V == 16 / sizeof(T): one 16-byte store per lane, fed by V / 4 float4 loads along the patch row
+// (p % V == 0, so a pack never leaves its patch row; pixels and patches 16-byte aligned).
+template <typename T, int V>
+__global__ __launch_bounds__(256) void patchify_keep_kernel(const float* __restrict__ px, int B, int H, int W, int p,
+                                                            const int32_t* __restrict__ keep, int K, T* __restrict__ out) {
+  const int gw = W / p, np = (H / p) * gw, Kd = 3 * p * p, Kv = Kd / V;
+  const int64_t total = (int64_t)B * K * Kv;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+    const int k = (int)(idx % Kv) * V;
+    const int64_t t = idx / Kv;  // b*K + j
+    const int b = (int)(t / K);
+    const int q = keep_at(keep, t, np);
+    const int pyi = q / gw, pxi = q % gw;
+    const int jj = k % p, i = (k / p) % p, c = k / (p * p);
+    const float* src = px + (((int64_t)b * 3 + c) * H + pyi * p + i) * W + pxi * p + jj;
+    if (V == 1) {
+      out[idx] = from_f<T>(src[0]);
+    } else {
+      Pack<T, V> o;
+#pragma unroll
+      for (int u = 0; u < V; u += 4) {
+        const float4 f = *reinterpret_cast<const float4*>(src + u);
+        o.v[u] = from_f<T>(f.x); o.v[u + 1] = from_f<T>(f.y); o.v[u + 2] = from_f<T>(f.z); o.v[u + 3] = from_f<T>(f.w);
+      }
+      st_pack<T, V>(out + idx * V, o);
+    }
+  }
+}
+template <typename T>
+static void launch_patchify_keep(const float* pixels, int B, int H, int W, int p, const int32_t* keep, int K, void* patches,
+                                 hipStream_t st) {
+  constexpr int V = PackOf<T>::N;
+  const int64_t elems = (int64_t)B * K * 3 * p * p;
+  const bool vec = p % V == 0 && d2r_aligned16(pixels) && d2r_aligned16(patches);
+  int blocks = d2r_cdiv(vec ? elems / V : elems, 256);
+  if (blocks > 4096) blocks = 4096;
+  if (vec) hipLaunchKernelGGL((patchify_keep_kernel<T, V>), dim3(blocks), dim3(256), 0, st, pixels, B, H, W, p, keep, K, (T*)patches);
+  else hipLaunchKernelGGL((patchify_keep_kernel<T, 1>), dim3(blocks), dim3(256), 0, st, pixels, B, H, W, p, keep, K, (T*)patches);
+}
+extern "C" int d2r_patchify_keep(int dtype, const float* pixels, int B, int H, int W, int p, const int32_t* h_keep,
+                                 const int32_t* keep, int K, void* patches, void* stream) {
+  D2R_REQUIRE(pixels && patches && B >= 1 && p >= 1 && H >= p && W >= p && H % p == 0 && W % p == 0, "d2r_patchify_keep: bad arguments");
+  D2R_REQUIRE(dtype == D2R_BF16 || dtype == D2R_F16 || dtype == D2R_F32, "d2r_patchify_keep: bad dtype %d", dtype);
+  D2R_REQUIRE((int64_t)(H / p) * (W / p) <= INT32_MAX / 2 && (int64_t)3 * p * p <= INT32_MAX / 2, "d2r_patchify_keep: image too large");
+  D2R_REQUIRE((reinterpret_cast<uintptr_t>(pixels) & 3u) == 0 && (reinterpret_cast<uintptr_t>(patches) & (d2r_esize(dtype) - 1)) == 0,
+              "d2r_patchify_keep: pixels / patches are not aligned to their element size");
+  if (int rc = check_keep("d2r_patchify_keep", h_keep, keep, B, K, (H / p) * (W / p))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == D2R_BF16) launch_patchify_keep<bf16_t>(pixels, B, H, W, p, keep, K, patches, st);
+  else if (dtype == D2R_F16) launch_patchify_keep<f16_t>(pixels, B, H, W, p, keep, K, patches, st);
+  else launch_patchify_keep<float>(pixels, B, H, W, p, keep, K, patches, st);
+  return d2r_check_launch("d2r_patchify_keep");
+}
+
+// x[b,0] = cls + pos[0]; x[b,1+j] += pos[1 + keep[b,j]]: clip_embed_finish_kernel's fp32 add and rounding per element, the table row
+// looked up.  V == 16 / sizeof(T): one 16-byte load and store of x per lane (D % V == 0, every pointer 16-byte aligned).
+template <typename T, int V>
+__global__ __launch_bounds__(256) void clip_embed_finish_keep_kernel(T* __restrict__ x, const float* __restrict__ cls,
+                                                                     const float* __restrict__ pos, const int32_t* __restrict__ keep,
+                                                                     int B, int K, int np, int D) {
+  const int Dv = D / V, ntok = K + 1;
+  const int64_t total = (int64_t)B * ntok * Dv;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+    const int d = (int)(idx % Dv) * V;
+    const int64_t row = idx / Dv;  // b*ntok + t
+    const int t = (int)(row % ntok);
+    const int64_t b = row / ntok;
+    const float* prow = pos + (int64_t)(t == 0 ? 0 : 1 + keep_at(keep, b * K + t - 1, np)) * D + d;
+    if (V == 1) {
+      const float base = t == 0 ? cls[d] : to_f<T>(x[idx]);
+      x[idx] = from_f<T>(base + prow[0]);
+    } else {
+      Pack<T, V> v;
+      if (t != 0) v = ld_pack<T, V>(x + idx * V);
+#pragma unroll
+      for (int u = 0; u < V; u += 4) {
+        const float4 pp = *reinterpret_cast<const float4*>(prow + u);
+        float4 bb;
+        if (t == 0) bb = *reinterpret_cast<const float4*>(cls + d + u);
+        else bb = make_float4(to_f<T>(v.v[u]), to_f<T>(v.v[u + 1]), to_f<T>(v.v[u + 2]), to_f<T>(v.v[u + 3]));
+        v.v[u] = from_f<T>(bb.x + pp.x); v.v[u + 1] = from_f<T>(bb.y + pp.y);
+        v.v[u + 2] = from_f<T>(bb.z + pp.z); v.v[u + 3] = from_f<T>(bb.w + pp.w);
+      }
+      st_pack<T, V>(x + idx * V, v);
+    }
+  }
+}
+template <typename T>
+static void launch_clip_embed_finish_keep(void* x, const float* cls, const float* pos, const int32_t* keep, int B, int K, int np,
+                                          int D, hipStream_t st) {
+  constexpr int V = PackOf<T>::N;
+  const int64_t elems = (int64_t)B * (K + 1) * D;
+  const bool vec = D % V == 0 && d2r_aligned16(x) && d2r_aligned16(cls) && d2r_aligned16(pos);
+  int blocks = d2r_cdiv(vec ? elems / V : elems, 256);
+  if (blocks > 4096) blocks = 4096;
+  if (vec) hipLaunchKernelGGL((clip_embed_finish_keep_kernel<T, V>), dim3(blocks), dim3(256), 0, st, (T*)x, cls, pos, keep, B, K, np, D);
+  else hipLaunchKernelGGL((clip_embed_finish_keep_kernel<T, 1>), dim3(blocks), dim3(256), 0, st, (T*)x, cls, pos, keep, B, K, np, D);
+}
+extern "C" int d2r_clip_embed_finish_keep(int dtype, void* x, const float* cls, const float* pos, const int32_t* h_keep,
+                                          const int32_t* keep, int B, int K, int np, int D, void* stream) {
+  D2R_REQUIRE(x && cls && pos && B >= 1 && D >= 1, "d2r_clip_embed_finish_keep: bad arguments");
+  D2R_REQUIRE(dtype == D2R_BF16 || dtype == D2R_F16 || dtype == D2R_F32, "d2r_clip_embed_finish_keep: bad dtype %d", dtype);
+  D2R_REQUIRE((reinterpret_cast<uintptr_t>(x) & (d2r_esize(dtype) - 1)) == 0 && ((reinterpret_cast<uintptr_t>(cls) | reinterpret_cast<uintptr_t>(pos)) & 3u) == 0,
+              "d2r_clip_embed_finish_keep: x / cls / pos are not aligned to their element size");
+  if (int rc = check_keep("d2r_clip_embed_finish_keep", h_keep, keep, B, K, np)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == D2R_BF16) launch_clip_embed_finish_keep<bf16_t>(x, cls, pos, keep, B, K, np, D, st);
+  else if (dtype == D2R_F16) launch_clip_embed_finish_keep<f16_t>(x, cls, pos, keep, B, K, np, D, st);
+  else launch_clip_embed_finish_keep<float>(x, cls, pos, keep, B, K, np, D, st);
+  return d2r_check_launch("d2r_clip_embed_finish_keep");
+}
+
+// dpos[0] = sum_b dX[b,0] (and dcls, the same bits); dpos[1+q] = the sum, in ascending b, of dX[b, 1+j] over the samples with
+// keep[b,j] == q; +0 where no sample kept q.  One block per table row.  Per 256 samples, lane i finds sample i's slot of q by a binary
+// search of its sorted keep row (-1: not kept) and leaves it in LDS; then every lane adds its columns over those samples in order -
+// batch_sum_rows_kernel's chain from 0.f, with the rows a position does not own left out.  No atomics.
+template <typename T>
+__global__ __launch_bounds__(256) void clip_embed_bwd_keep_kernel(const T* __restrict__ dX, const int32_t* __restrict__ keep, int B,
+                                                                  int K, int np, int D, float* __restrict__ dcls,
+                                                                  float* __restrict__ dpos) {
+  __shared__ int slot[256];
+  const int t = blockIdx.x, q = t - 1, ntok = K + 1;  // t in [0, np]
+  for (int d0 = 0; d0 < D; d0 += 1024) {
+    float s[4] = {0.f, 0.f, 0.f, 0.f};  // columns d0 + threadIdx.x + 256 u
+    for (int b0 = 0; b0 < B; b0 += 256) {
+      const int nb = min(256, B - b0);
+      __syncthreads();
+      if ((int)threadIdx.x < nb) {
+        int j = 0;
+        if (t != 0) {
+          const int32_t* row = keep + (int64_t)(b0 + threadIdx.x) * K;
+          int lo = 0, hi = K;  // the first slot with row[slot] >= q
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (row[mid] < q) lo = mid + 1; else hi = mid;
+          }
+          j = (lo < K && row[lo] == q) ? lo + 1 : -1;
+        }
+        slot[threadIdx.x] = j;
+      }
+      __syncthreads();
+      for (int i = 0; i < nb; ++i) {
+        const int j = slot[i];
+        if (j < 0) continue;
+        const T* src = dX + ((int64_t)(b0 + i) * ntok + j) * D + d0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int c = threadIdx.x + 256 * u;
+          if (d0 + c < D) s[u] += to_f<T>(src[c]);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int c = d0 + threadIdx.x + 256 * u;
+      if (c < D) {
+        dpos[(int64_t)t * D + c] = s[u];
+        if (t == 0) dcls[c] = s[u];
+      }
+    }
+  }
+}
+extern "C" int d2r_clip_embed_bwd_keep(int dtype, const void* dX, const int32_t* h_keep, const int32_t* keep, int B, int K, int np,
+                                       int D, float* dcls, float* dpos, void* stream) {
+  D2R_REQUIRE(dX && dcls && dpos && B >= 1 && D >= 1, "d2r_clip_embed_bwd_keep: bad arguments");
+  D2R_REQUIRE(dtype == D2R_BF16 || dtype == D2R_F16 || dtype == D2R_F32, "d2r_clip_embed_bwd_keep: bad dtype %d", dtype);
+  D2R_REQUIRE((reinterpret_cast<uintptr_t>(dX) & (d2r_esize(dtype) - 1)) == 0 && ((reinterpret_cast<uintptr_t>(dcls) | reinterpret_cast<uintptr_t>(dpos)) & 3u) == 0,
+              "d2r_clip_embed_bwd_keep: dX / dcls / dpos are not aligned to their element size");
+  if (int rc = check_keep("d2r_clip_embed_bwd_keep", h_keep, keep, B, K, np)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(np + 1), block(256);
+  if (dtype == D2R_BF16) hipLaunchKernelGGL((clip_embed_bwd_keep_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)dX, keep, B, K, np, D, dcls, dpos);
+  else if (dtype == D2R_F16) hipLaunchKernelGGL((clip_embed_bwd_keep_kernel<f16_t>), grid, block, 0, st, (const f16_t*)dX, keep, B, K, np, D, dcls, dpos);
+  else hipLaunchKernelGGL((clip_embed_bwd_keep_kernel<float>), grid, block, 0, st, (const float*)dX, keep, B, K, np, D, dcls, dpos);
+  return d2r_check_launch("d2r_clip_embed_bwd_keep");
+}

@@ -2172,3 +2172,64 @@ def image_mix(pixels: torch.Tensor, h_desc: torch.Tensor, desc: torch.Tensor) ->
 
 def clip_embed(pixels, w_master, w_compute, cls, pos, patch):
     return _ClipEmbed.apply(pixels, w_master, w_compute, cls, pos, patch)
+
+
+class _ClipEmbedKeep(torch.autograd.Function):
+    """_ClipEmbed on a kept subset of the patches (PatchDropout, K25): keep int32 [B, K] on the device, h_keep its host copy, every
+    row strictly increasing -> [B, 1 + K, E].  Only the kept patches are unfolded, multiplied and saved."""
+
+    @staticmethod
+    def forward(ctx, pixels, w_master, w_compute, cls, pos, patch, h_keep, keep):
+        pixels = pixels.contiguous().float()
+        B, _, Hh, Ww = pixels.shape
+        E = w_compute.shape[0]
+        K = 3 * patch * patch
+        npatch = (Hh // patch) * (Ww // patch)
+        nkeep = keep.shape[1]
+        ntok = nkeep + 1
+        dtype = w_compute.dtype
+        patches = torch.empty(B * nkeep, K, dtype=dtype, device=pixels.device)
+        _lib.call("d2r_patchify_keep", _dt(patches), pixels.data_ptr(), B, Hh, Ww, patch, h_keep.data_ptr(), keep.data_ptr(), nkeep,
+                  patches.data_ptr(), _stream())
+        x = torch.empty(B, ntok, E, dtype=dtype, device=pixels.device)
+        w2 = w_compute.view(E, K)
+        es = x.element_size()
+        gemm(GEMM_NT, nkeep, E, K, patches.data_ptr(), K, w2.data_ptr(), K, x.data_ptr() + E * es, E, dtype=_dt(x),
+             c_dtype=_dt(x), nb=B, sA=(nkeep * K, 0), sC=(ntok * E, 0))
+        _lib.call("d2r_clip_embed_finish_keep", _dt(x), x.data_ptr(), cls.data_ptr(), pos.data_ptr(), h_keep.data_ptr(),
+                  keep.data_ptr(), B, nkeep, npatch, E, _stream())
+        ctx.save_for_backward(patches, keep)
+        ctx.h_keep = h_keep  # the host copy lives as long as the graph: the backward call checks it again
+        ctx.meta = (B, npatch, nkeep, E, K, tuple(w_master.shape))
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        patches, keep = ctx.saved_tensors
+        B, npatch, nkeep, E, K, wshape = ctx.meta
+        g = g.contiguous()
+        dcls = torch.empty(E, dtype=torch.float32, device=g.device)
+        dpos = torch.empty(npatch + 1, E, dtype=torch.float32, device=g.device)
+        _lib.call("d2r_clip_embed_bwd_keep", _dt(g), g.data_ptr(), ctx.h_keep.data_ptr(), keep.data_ptr(), B, nkeep, npatch, E,
+                  dcls.data_ptr(), dpos.data_ptr(), _stream())
+        # dW[E,K] = dY_patch^T patches over the B*K kept rows: _ClipEmbed's strided copy and ONE split-K weight-gradient GEMM
+        dw = torch.empty(E, K, dtype=torch.float32, device=g.device)
+        gp = g[:, 1:, :].contiguous()
+        gemm(GEMM_TN, E, K, B * nkeep, gp.data_ptr(), E, patches.data_ptr(), K, dw.data_ptr(), K, dtype=_dt(g), c_dtype=F32,
+             beta=0.0, splitk_ws=_workspace(64 << 20, g.device))
+        return None, dw.view(wshape), None, dcls, dpos, None, None, None
+
+
+def clip_embed_keep(pixels, w_master, w_compute, cls, pos, patch, h_keep, keep):
+    """clip_embed with PatchDropout: sample b keeps the patches keep[b] (d2r_amd.patch_dropout draws them).  h_keep: contiguous
+    int32 [B, K] on the host; keep: the same values on the pixels' device.  A bad keep set is refused by the C entry points."""
+    B = pixels.shape[0]
+    for t, where in ((h_keep, "cpu"), (keep, pixels.device.type)):
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1 or t.device.type != where or not t.is_contiguous():
+            raise _lib.D2RError(f"clip_embed_keep: the kept positions must be contiguous int32 [{B}, K], one on the host and one on "
+                                "the pixels' device")
+    if tuple(h_keep.shape) != tuple(keep.shape):
+        raise _lib.D2RError(f"clip_embed_keep: host copy {tuple(h_keep.shape)} and device copy {tuple(keep.shape)} differ in shape")
+    if keep.is_cuda:
+        keep.record_stream(torch.cuda.current_stream())  # drawn by whoever calls; read here, on the vision branch's stream
+    return _ClipEmbedKeep.apply(pixels, w_master, w_compute, cls, pos, patch, h_keep, keep)

@@ -777,9 +777,14 @@ class CLIPVisionEmbeddings(D2RModule):
         self.num_positions = self.num_patches + 1
         self.position_embedding = _Embedding(self.num_positions, self.embed_dim)
         self.register_buffer("position_ids", torch.arange(self.num_positions).expand((1, -1)))
+        self.patch_dropout = None  # a d2r_amd.patch_dropout.PatchDropout, training only (UnimoModel.set_patch_dropout)
 
     def forward(self, pixel_values):
         w = self.patch_embedding.weight
+        if self.training and self.patch_dropout is not None:  # K of the np patches per sample; the rest never enter the tower
+            h_keep, keep = self.patch_dropout.sample(pixel_values.shape[0], pixel_values.device)
+            return F.clip_embed_keep(pixel_values, w, _compute_weight(w, self.cdtype), self.class_embedding,
+                                     self.position_embedding.weight, self.patch_size, h_keep, keep)
         return F.clip_embed(pixel_values, w, _compute_weight(w, self.cdtype), self.class_embedding,
                             self.position_embedding.weight, self.patch_size)
 
@@ -890,6 +895,16 @@ class UnimoModel(D2RModule):
             for layer, r in zip(layers, rs):
                 layer.p_path = r
         return rates
+
+    def set_patch_dropout(self, p: float, seed: int = 0, rank: int = 0):
+        """PatchDropout (an extension, off by default): in train() mode every image keeps its class token and K = max(1, int(np *
+        (1 - p))) of its np patches, drawn per sample by a generator seeded from (seed, rank); the vision tower, the vision self layer
+        and both routing modules run on 1 + K image tokens.  p = 0 clears it: no generator, no draw, the model as it was built.
+        Returns the sampler (d2r_amd.patch_dropout.PatchDropout) or None."""
+        from .patch_dropout import PatchDropout, check_rate
+        emb = self.vision_embeddings
+        emb.patch_dropout = PatchDropout(p, emb.num_patches, seed=seed, rank=rank) if check_rate(p) > 0.0 else None
+        return emb.patch_dropout
 
     def _head_bundle(self, fc):
         """The cached HeadBundle when the one-call head applies (fp32 parameters with gradient sinks, the 20 + 20 merge groups

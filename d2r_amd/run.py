@@ -27,6 +27,8 @@ tensors on the device (d2r_token_augment, d2r_amd.text_augment, DESIGN.md K23); 
 --aug_mixup A / --aug_cutmix A / --aug_mix_prob P: MixUp / CutMix of the finished training pixel batch in one launch, with a cross
 entropy against two labels per sample (d2r_image_mix, d2r_ce_mix_*, d2r_amd.mix); only the image is mixed; real and
 synthetic data.
+--patch_dropout P: PatchDropout of the vision tower: a training image keeps its class token and max(1, int(np * (1 - P))) of its np
+patches, and everything behind the embedding runs on the shorter sequence (d2r_amd.patch_dropout); training only.
 """
 from __future__ import annotations
 
@@ -179,6 +181,13 @@ def _drop_path(text):
     return v
 
 
+def _patch_dropout(text):
+    v = float(text)
+    if not (math.isfinite(v) and 0 <= v < 1):
+        raise argparse.ArgumentTypeError(f"must be in [0, 1) (0 = off), got {text}")
+    return v
+
+
 def parse_class_weights(text, num_classes):
     """--class_weights: 'none' -> None, 'balanced' -> 'balanced' (resolved from the training split), 'W0,W1,...' -> the list of
     num_classes non-negative finite floats, not all zero.  Anything else: ValueError."""
@@ -293,6 +302,11 @@ def build_parser():
                    "training, encoder layer i of L drops each of its two residual branches per sample with probability P * i / (L - 1) "
                    "and scales it by the inverse of the rest otherwise (timm's / BEiT's linear schedule); in [0, 1), 0 = off, the "
                    "reference's behaviour; dev, test and prediction passes are never affected")
+    p.add_argument("--patch_dropout", default=0.0, type=_patch_dropout, help="PatchDropout (Liu et al. 2022; open_clip's "
+                   "--force-patch-dropout): in training, every image keeps its class token and K = max(1, int(np * (1 - P))) of its np "
+                   "patches, drawn per sample, and the vision tower, the vision self layer and both routing modules run on 1 + K image "
+                   "tokens (d2r_patchify_keep, d2r_clip_embed_finish_keep, d2r_clip_embed_bwd_keep); in [0, 1), 0 = off, the reference's "
+                   "behaviour; dev, test and prediction passes always see all patches; real and synthetic data")
     p.add_argument("--label_smoothing", default=0.0, type=_label_smoothing, help="label smoothing of the cross entropy, in [0, 1), as "
                    "torch.nn.CrossEntropyLoss(label_smoothing=) (0 = off, the reference's behaviour); training, dev and test loss alike")
     p.add_argument("--class_weights", default="none", type=str, help="per-class weights of the cross entropy, as "
@@ -536,6 +550,9 @@ def main(argv=None):
     if args.only_test and args.drop_path:
         logger.info("--drop_path is ignored with --only_test: stochastic depth acts on training steps only")
         args.drop_path = 0.0
+    if args.only_test and args.patch_dropout:
+        logger.info("--patch_dropout is ignored with --only_test: patches are dropped in training steps only")
+        args.patch_dropout = 0.0
     if class_weights == "balanced":
         try:
             class_weights = balanced_class_weights(train_label_counts(args, None if args.data_path is None else files[0]))

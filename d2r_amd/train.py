@@ -12,7 +12,9 @@ state-dict key names (:210-216).  Differences, all deliberate (SURVEY.md Appendi
   * optional extensions: gradient clipping (args.max_grad_norm) and a weight EMA (args.ema_decay: evaluate() / test() run on
     the averaged weights and best_model.pth holds them; BatchNorm running statistics stay the live ones), layer-wise lr decay and
     no weight decay on 1-D parameters (args.layer_lr_decay, args.wd_exempt_1d), the weight decay itself (args.weight_decay),
-    stochastic depth of the two encoder towers in training steps (args.drop_path; its seeds come from a generator of its own);
+    stochastic depth of the two encoder towers in training steps (args.drop_path; its seeds come from a generator of its own),
+    PatchDropout of the vision tower in training steps (args.patch_dropout, d2r_amd.patch_dropout: a sampler with a generator of
+    its own on the vision embedding; evaluate() / test() / predict() see all patches);
   * optional image augmentation of the TRAINING batches (``augmenter``, d2r_amd.augment: random resized crop and flip, colour
     jitter, random grayscale and random erasing on the device; a CachedLoader carries its own); evaluate() / test() / predict()
     never augment;
@@ -189,6 +191,12 @@ class MSDTrainer:
         if rate > 0.0 and self.train_data is not None:
             self.drop_path_rates = self.model.model.set_drop_path(rate)
             F.seed_drop_path(int(getattr(self.args, "seed", 0)), self.dp.rank)
+        # PatchDropout: a sampler on the vision embedding with a generator of its own, seeded from (seed, rank); K depends on the
+        # flag and the patch grid alone, so it is the same on every rank.  Off (0) builds no generator and leaves the model as it was.
+        self.patch_dropout = None
+        rate = float(getattr(self.args, "patch_dropout", 0.0) or 0.0)
+        if rate > 0.0 and self.train_data is not None:
+            self.patch_dropout = self.model.model.set_patch_dropout(rate, int(getattr(self.args, "seed", 0)), self.dp.rank)
         if self.train_data is not None:
             self.scheduler = LinearWarmupSchedule(self.optimizer, self.args.warmup_ratio * self.train_num_steps,
                                                   self.train_num_steps)
@@ -239,6 +247,8 @@ class MSDTrainer:
         if self.drop_path_rates is not None:
             self.logger.info("  Stochastic depth (training steps only): drop_path per layer, text tower [%s], vision tower [%s]",
                              *(", ".join(f"{r:.4g}" for r in rs) for rs in self.drop_path_rates))
+        if self.patch_dropout is not None:
+            self.logger.info("  PatchDropout (training steps only): %s", self.patch_dropout.describe())
         augmenter = self.augmenter or getattr(self.train_data, "augmenter", None)
         if augmenter is not None:
             self.logger.info("  Image augmentation of the training batches: %s", augmenter.describe())

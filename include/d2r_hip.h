@@ -802,6 +802,34 @@ int d2r_clip_cache_augment_photo(const uint8_t* cache, int64_t cache_rows, const
  * [1, 65535], S outside [1, 4096], in / out / desc not 4-byte aligned, out overlapping in, a partner outside [0, B), an a that is
  * not finite or outside [0, 1], a negative w or h, a box that does not lie inside [0, S] x [0, S]. */
 int d2r_image_mix(const float* in, float* out, int B, int S, const int32_t* h_desc, const int32_t* desc, void* stream);
+/* K25  PatchDropout (d2r_amd/patch_dropout.py, --patch_dropout): the vision embedding on a kept subset of the patches.  Every sample keeps
+ * its class token and K of its np patches; d2r_patchify, d2r_clip_embed_finish and d2r_clip_embed_bwd each get a form that takes the
+ * kept positions, so that the dropped patches are never read, never multiplied and never enter the tower.
+ *   keep / h_keep : int32 [B, K] on the device and its host copy: per sample the kept patch positions (raster order, 0 .. np-1),
+ *                   strictly increasing.
+ * Checked on h_keep before anything is enqueued (a refused call writes nothing, d2r_last_error names the entry point): a null pointer,
+ * B < 1, K outside [1, np], an index outside [0, np), a row that is not strictly increasing (a repeated index included), a bad dtype,
+ * a pointer that is not aligned to its element size, and what the entry point's counterpart refuses.
+ *
+ * d2r_patchify_keep: patches[b*K + j, (c*p + i)*p + jj] = pixels[b, c, py*p + i, px*p + jj] with (py, px) = (keep[b,j] / (W/p),
+ * keep[b,j] % (W/p)); patches is T [B*K, 3*p*p], OVERWRITTEN; only kept patches are read.  float4 loads along a patch row and one
+ * 16-byte store per 8 (16-bit) or 4 (fp32) elements when p is a multiple of that count and pixels and patches are 16-byte aligned
+ * (p = 16, 32), element by element otherwise (p = 14); both give the same bits.
+ *
+ * d2r_clip_embed_finish_keep: in place on x [B, 1+K, D], rows 1.. holding the patch GEMM output: x[b,0] = cls + pos[0];
+ * x[b,1+j] = x[b,1+j] + pos[1 + keep[b,j]].  pos is fp32 [1+np, D]; the add is in fp32 and rounded once, as d2r_clip_embed_finish's.
+ *
+ * d2r_clip_embed_bwd_keep: dX is [B, 1+K, D]; dpos fp32 [1+np, D] and dcls fp32 [D] are OVERWRITTEN: dpos[0] = sum_b dX[b,0];
+ * dpos[1+q] = the sum of dX[b, 1+j] over the samples b with keep[b,j] == q, in ascending b, in fp32 from 0.f; a position no sample
+ * kept gets +0; dcls = dpos[0].  No atomics: a second run gives the same bits.
+ *
+ * With K == np and keep[b,j] == j each of the three writes bit for bit what its counterpart writes. */
+int d2r_patchify_keep(int dtype, const float* pixels, int B, int H, int W, int p, const int32_t* h_keep, const int32_t* keep, int K,
+                      void* patches, void* stream);
+int d2r_clip_embed_finish_keep(int dtype, void* x, const float* cls, const float* pos, const int32_t* h_keep, const int32_t* keep,
+                               int B, int K, int np, int D, void* stream);
+int d2r_clip_embed_bwd_keep(int dtype, const void* dX, const int32_t* h_keep, const int32_t* keep, int B, int K, int np, int D,
+                            float* dcls, float* dpos, void* stream);
 /* K23  Text augmentation on the token rows (d2r_amd/text_augment.py, --aug_token_delete / --aug_token_mask / --aug_token_replace /
  * --aug_whole_word).  d2r_token_augment builds the three token tensors of a batch from their source rows - what three d2r_gather_rows
  * calls do - and deletes, masks or replaces tokens per sample on the way.
